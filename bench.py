@@ -18,7 +18,14 @@ xGMI (--exchange mailbox, default; --exchange rccl: one ncclAllGather), and
 every rank runs the same placement (strong scaling).  --mode replicas: N
 independent sessions.
 
-Also reported:
+A plain run sets up, warms up, times the steps, writes the last step's
+placements if --dump-outputs is given, and prints the result line; its roofline
+holds what the timed steps' own counters give.  --dump-outputs DIR writes the
+placement log of the last timed step, in log order, as DIR/pod.npy, DIR/node.npy
+and DIR/kind.npy (float64; kind 1 = allocated, else pipelined): the snapshot is
+generated from a fixed seed, so two builds can be compared array for array.
+
+With --full, also reported (each takes runs of its own, after the timed steps):
 * roofline of the batched pop path: with the persistent pop engine (default,
   --engine 1: k_engine, one resident kernel serving every eligible pop from a
   descriptor ring) or the fused pop kernel (--engine 0: k_pop_batch_ov, sweep
@@ -70,9 +77,15 @@ def parse():
     ap.add_argument("--nodes", type=int, default=100_000)
     ap.add_argument("--pending", type=int, default=800_000)
     ap.add_argument("--cache", default=os.environ.get("KBHIP_BENCH_CACHE", "/tmp/kbhip_bench"))
-    ap.add_argument("--cpu-baseline", type=int, default=1, help="1 = time the CPU restatement on rank 0")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run the CPU baseline, the standalone sweep roofline and the "
+                         "committed counter summaries (off: the run does only what the result line's value needs)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's placement log as DIR/pod.npy, DIR/node.npy, DIR/kind.npy")
+    ap.add_argument("--cpu-baseline", type=int, default=1,
+                    help="with --full: 1 = time the CPU restatement on rank 0")
     ap.add_argument("--sweep-nodes", type=int, default=4_000_000,
-                    help="node count of the standalone sweep's at-scale line (roofline.sweep.at_scale; 0 = none)")
+                    help="with --full: node count of the standalone sweep's at-scale line (roofline.sweep.at_scale; 0 = none)")
     ap.add_argument("--cpu-seconds", type=float, default=15.0, help="target CPU baseline sample length")
     ap.add_argument("--time-every", type=int, default=50,
                     help="HIP-event time every k-th batched pop launch on its own stream (the roofline's kernel "
@@ -98,6 +111,8 @@ def parse():
                     help="shard mode: batched pops exchange their top-64 lists through peer mailboxes written by "
                          "the kernels over xGMI (default; kbhip_shard_connect_mailbox), or one ncclAllGather per pop")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     EXCHANGE_MODE[0] = args.exchange
     return args
 
@@ -370,6 +385,13 @@ def cpu_baseline(path, target_s, log):
                       f"extrapolated per stratum"}
 
 
+def dump_outputs(d, log):
+    """The arrays allocate() returned in the last timed step, one .npy each."""
+    os.makedirs(d, exist_ok=True)
+    for name, a in zip(("pod", "node", "kind"), log):
+        np.save(os.path.join(d, name + ".npy"), np.asarray(a).astype(np.float64))
+
+
 def main():
     args = parse()
     rank, world, local, dist = dist_setup(args.gpus)
@@ -389,9 +411,12 @@ def main():
     t0 = time.perf_counter()
     lat, placed, sweeps_ms, sweeps_n, st_last = [], 0, 0.0, 0, None
     dev_s, dev_pops = 0.0, 0
+    log0 = log_last = None
     for i in range(args.steps):
         dt, n, st = run_session(buf, device, args.time_every, shard, args.overlap,
-                                args.speculate, keep_log=(i == 0 and rank == 0), engine=args.engine,
+                                args.speculate, keep_log=(rank == 0 and ((i == 0 and args.full) or
+                                                        (i == args.steps - 1 and bool(args.dump_outputs)))),
+                                engine=args.engine,
                                 engine_workers=args.engine_workers, engine_lists=args.engine_lists,
                                 engine_groups=args.engine_groups)
         lat.append(dt)
@@ -401,7 +426,9 @@ def main():
         dev_s += st["alloc_device_s"]
         dev_pops += st["batched_pops"]
         if "log" in st:
-            log0 = st.pop("log")
+            log_last = st.pop("log")
+            if i == 0:
+                log0 = log_last
         st_last = st
     barrier(dist, local)
     wall = time.perf_counter() - t0
@@ -412,9 +439,11 @@ def main():
         if dist is not None:
             dist.destroy_process_group()
         return
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, log_last)
     nodes = st_last["nodes"]
-    traffic = None if shard else pmc_traffic(st_last["engine_pops"] > 0)
-    sweep = None if shard else sweep_roofline(buf, device, log0[0], args.cache, args.sweep_nodes)
+    traffic = pmc_traffic(st_last["engine_pops"] > 0) if args.full and not shard else None
+    sweep = sweep_roofline(buf, device, log0[0], args.cache, args.sweep_nodes) if args.full and not shard else None
     nodes_per_launch = (nodes + world - 1) // world if shard else nodes  # a shard sweeps its own range
     # the hot kernel's mean duration: HIP events around every batched pop launch on the stream it runs on
     # (overlapped pops: the duration includes the wait for the previous pop's write-back, as rocprof's does)
@@ -480,7 +509,7 @@ def main():
         out["roofline"]["span_timing"] = (f"each launch's own start-to-end span (HIP events around every "
                                           f"{args.time_every}-th launch on its stream, {sweeps_n} launches): it "
                                           f"includes the wait for the previous pop, so consecutive spans overlap")
-    if args.cpu_baseline and world == 1:
+    if args.full and args.cpu_baseline and world == 1:
         out["cpu_baseline"] = cpu_baseline(path, args.cpu_seconds, log0)
         out["cpu_baseline"]["gpu_p50_session_ms"] = out["p50_session_ms"]
     print(json.dumps(out))

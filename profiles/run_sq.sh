@@ -20,5 +20,5 @@ timeout -k 10 300 python3 -u profiles/phases.py 2 1 > $OUT/phases_ov.json
 timeout -k 10 300 python3 -u profiles/phases.py 2 0 > $OUT/phases.json
 if [ -n "$PMC" ]; then
     timeout -s KILL 600 rocprofv3 --pmc $PMC --kernel-trace -d $OUT/pmc -o run --output-format csv -- \
-        python3 bench.py --steps 1 --warmup 0 --cpu-baseline 0 > $OUT/bench_pmc.json
+        python3 bench.py --full --steps 1 --warmup 0 --cpu-baseline 0 > $OUT/bench_pmc.json
 fi
