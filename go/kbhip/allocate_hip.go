@@ -96,13 +96,51 @@ func (a *allocateHIPAction) Execute(ssn *framework.Session) {
 }
 
 // apply one placement through the reference's session (allocate.go:161-181).
+// The over-backfill flag is false, as in the reference: allocate.go:153 calls
+// node.GetAccessibleResource() first, which adds Backfilled to node.Idle in
+// place (node_info.go:209-211), so the !InitResreq.LessEqual(node.Idle) of
+// allocate.go:157 is evaluated on an Idle the task already fits.
 func apply(ssn *framework.Session, task *api.TaskInfo, host string, kind uint8) error {
 	if kind == Allocated {
-		// usingBackfillTaskRes: InitResreq does not fit Idle alone (allocate.go:161)
-		node := ssn.Nodes[host]
-		return ssn.Allocate(task, host, !task.InitResreq.LessEqual(node.Idle))
+		return ssn.Allocate(task, host, false)
 	}
 	return ssn.Pipeline(task, host)
+}
+
+// applyVisits replays the GetAccessibleResource side effect of the walks the
+// device ran since the last call (kbhip_walk_visits) on the session's own
+// NodeInfo objects: Idle += Backfilled once per visit.  Called before the
+// placements of those walks are applied, so that node.Idle never goes negative
+// and the later backfill and preempt actions read the Idle the reference
+// would have left.
+func applyVisits(ssn *framework.Session, eng *Engine, idx *Index) error {
+	visits, err := eng.WalkVisits()
+	if err != nil {
+		return err
+	}
+	for _, v := range visits {
+		node := ssn.Nodes[idx.NodeNames[v.Node]]
+		for k := uint32(0); k < v.Count; k++ {
+			node.GetAccessibleResource()
+		}
+	}
+	return nil
+}
+
+// setFitDelta fills job.NodesFitDelta from the device's records of the task
+// that ended the pop unassigned (allocate.go:124-126 resets the map at every
+// pop, :164-167 fills it while the task's walk passes nodes that do not fit).
+func setFitDelta(job *api.JobInfo, eng *Engine, idx *Index, task int32) error {
+	recs, err := eng.FitDeltas(task)
+	if err != nil {
+		return err
+	}
+	job.NodesFitDelta = make(api.NodeResourceMap, len(recs))
+	for _, r := range recs {
+		job.NodesFitDelta[idx.NodeNames[r.Node]] = &api.Resource{
+			MilliCPU: float64(r.MilliCPU), Memory: float64(r.Memory), MilliGPU: float64(r.MilliGPU)}
+	}
+	return nil
 }
 
 // executeWhole: kbhip_allocate places every pop with its C++ mirror of the
@@ -113,6 +151,13 @@ func apply(ssn *framework.Session, task *api.TaskInfo, host string, kind uint8) 
 func executeWhole(ssn *framework.Session, eng *Engine, idx *Index) error {
 	log, err := eng.Allocate(len(idx.Pods) + 1)
 	if err != nil {
+		return err
+	}
+	// every walk's Idle += Backfilled first (the sum commutes with the placements' Idle -= Resreq;
+	// a session that places backfill-annotated pending tasks needs PerPop, where the counts are
+	// read after each pop).  NodesFitDelta is not filled in this mode: the close messages come
+	// from eng.GangUnschedulable.
+	if err := applyVisits(ssn, eng, idx); err != nil {
 		return err
 	}
 	for _, p := range log {
@@ -177,6 +222,18 @@ func executePerPop(ssn *framework.Session, eng *Engine, idx *Index) error {
 			nodes, kinds, stop, err := eng.PlaceJob(ids, gang, job.MinAvailable, ready)
 			if err != nil {
 				return err
+			}
+			if err := applyVisits(ssn, eng, idx); err != nil {
+				return err
+			}
+			job.NodesFitDelta = make(api.NodeResourceMap) // allocate.go:124-126
+			if stop == StopUnassigned && len(nodes) > 0 {
+				// StopAll pops that leave the job not Ready keep the nodes ahead of the last task's
+				// node in the reference's map; the device reports those as a histogram only
+				// (eng.GangUnschedulable), see INTEGRATION.md
+				if err := setFitDelta(job, eng, idx, ids[len(nodes)-1]); err != nil {
+					return err
+				}
 			}
 			for i := range nodes {
 				if nodes[i] < 0 {

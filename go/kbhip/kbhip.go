@@ -155,6 +155,67 @@ func (e *Engine) Wait(ticket int64, n int) (nodes []int32, kinds []uint8, stop i
 
 func (e *Engine) Cancel(ticket int64) { C.kbhip_place_job_cancel(e.s, C.int64_t(ticket)) }
 
+// Visit is one entry of kbhip_walk_visits: a node the allocate walks reached
+// and how many times (each time node.GetAccessibleResource() added the node's
+// Backfilled to its Idle, node_info.go:209-211).
+type Visit struct {
+	Node  int32
+	Count uint32
+}
+
+// WalkVisits returns the nodes with Backfilled resources that the walks since
+// the previous call visited, in ascending node index, and clears the counts.
+func (e *Engine) WalkVisits() ([]Visit, error) {
+	n := C.kbhip_walk_visits(e.s, nil, nil, 0)
+	if n < 0 {
+		return nil, lastErr("walk_visits", C.int(n))
+	}
+	if n == 0 {
+		return nil, nil
+	}
+	nodes := make([]int32, int(n))
+	counts := make([]uint32, int(n))
+	if m := C.kbhip_walk_visits(e.s, (*C.int32_t)(unsafe.Pointer(&nodes[0])),
+		(*C.uint32_t)(unsafe.Pointer(&counts[0])), n); m < 0 {
+		return nil, lastErr("walk_visits", C.int(m))
+	}
+	out := make([]Visit, int(n))
+	for i := range out {
+		out[i] = Visit{Node: nodes[i], Count: counts[i]}
+	}
+	return out, nil
+}
+
+// FitDelta is one record of kbhip_fit_deltas: node.Idle.Clone().FitDelta(
+// task.Resreq) of a node the task's walk visited (allocate.go:164-167).
+type FitDelta struct {
+	Node                     int32
+	MilliCPU, Memory, MilliGPU int64
+}
+
+// FitDeltas returns job.NodesFitDelta for the task on which the most recent
+// pop stopped unassigned, in ascending node index.
+func (e *Engine) FitDeltas(task int32) ([]FitDelta, error) {
+	n := C.kbhip_fit_deltas(e.s, C.int32_t(task), nil, nil, 0)
+	if n < 0 {
+		return nil, lastErr("fit_deltas", C.int(n))
+	}
+	if n == 0 {
+		return nil, nil
+	}
+	nodes := make([]int32, int(n))
+	deltas := make([]int64, 3*int(n))
+	if m := C.kbhip_fit_deltas(e.s, C.int32_t(task), (*C.int32_t)(unsafe.Pointer(&nodes[0])),
+		(*C.int64_t)(unsafe.Pointer(&deltas[0])), n); m < 0 {
+		return nil, lastErr("fit_deltas", C.int(m))
+	}
+	out := make([]FitDelta, int(n))
+	for i := range out {
+		out[i] = FitDelta{Node: nodes[i], MilliCPU: deltas[3*i], Memory: deltas[3*i+1], MilliGPU: deltas[3*i+2]}
+	}
+	return out, nil
+}
+
 // GangUnschedulable is the gang plugin's OnSessionClose text after Allocate
 // (gang.go:166-187): "<job uid>\t<message>\n" per job that is not ready.
 func (e *Engine) GangUnschedulable() (string, error) {

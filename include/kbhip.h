@@ -391,6 +391,52 @@ int kbhip_set_option(kb_session* s, const char* key, int64_t value);
  * Returns the text length; copies it (NUL-terminated) when cap > length. */
 int64_t kbhip_gang_unschedulable(kb_session* s, char* out, int64_t cap);
 
+/* Read-outs of the allocate walk (allocate.go:149-185), for a host that keeps
+ * the reference's own NodeInfo and JobInfo objects beside the engine.
+ *
+ * kbhip_walk_visits <- the GetAccessibleResource side effect (node_info.go:
+ *   209-211: Idle.Add(Backfilled) mutates Idle in place): every node a task's
+ *   walk reaches — the nodes ahead of the chosen one and the chosen one, or
+ *   every node of the walk when the task finds none — gets Backfilled added to
+ *   its Idle once per visit.  The device applies this to its own Idle column
+ *   and counts the visits of every node whose Backfilled is not zero (on the
+ *   others the call changes nothing).  The call returns the nodes with a
+ *   non-zero count since the previous call, in ascending node index, with
+ *   their counts (out_node / out_count, `cap` entries each), clears the
+ *   counters it returned and returns the number of entries.  When cap is
+ *   smaller than that number (null outputs with cap 0: the size query) only
+ *   the number is returned and nothing is cleared.  A host applies
+ *   node.GetAccessibleResource() out_count[i] times to node out_node[i] before
+ *   it applies the pop's placements; per node, at any quiescent point,
+ *     Idle == Idle at open + visits x Backfilled - committed requests.
+ *   The backfill, reclaim and preempt actions never call
+ *   GetAccessibleResource.  A count multiplies the node's Backfilled as it is
+ *   when the host applies it: where a session places backfill-annotated
+ *   pending tasks (which raise Backfilled) the counts are read after every
+ *   pop.  The counters restart at every carry-over.
+ * kbhip_fit_deltas <- job.NodesFitDelta of a task that found no node
+ *   (allocate.go:164-167): for the task on which the session's most recent job
+ *   pop stopped with KBHIP_STOP_UNASSIGNED (kbhip_place_job / _wait, or the
+ *   last pop inside kbhip_allocate), one record per node that passed
+ *   PredicateFn and got a NodeOrderFn score — each was visited and did not
+ *   fit — in ascending node index: out_node[i] and out_delta[3 i ..] = (cpu,
+ *   memory, GPU) of node.Idle.Clone().FitDelta(task.Resreq)
+ *   (resource_info.go:134-147: Idle - (Resreq + min) where Resreq > 0, else
+ *   Idle), Idle after the walk's own visit.  Nothing is committed after such a
+ *   walk, so the records are computed from the current node state by one sweep
+ *   that compacts them on the device; only the records are copied back.
+ *   Returns their number; copies when cap is at least that.  KBHIP_EINVAL for
+ *   any other task_id, and after any later call that runs an action, places a
+ *   job or carries the session.  A pop that places every given task and leaves
+ *   its job not Ready (KBHIP_STOP_ALL) is not covered: there NodesFitDelta
+ *   holds the nodes ahead of the last task's chosen node, which only the state
+ *   at walk time gives exactly; kbhip_gang_unschedulable's histogram text
+ *   remains the source for those jobs.
+ * Both fail with KBHIP_EINVAL while submitted pops are outstanding and with
+ * KBHIP_EUNSUPPORTED on node-sharded sessions. */
+int64_t kbhip_walk_visits(kb_session* s, int32_t* out_node, uint32_t* out_count, int64_t cap);
+int64_t kbhip_fit_deltas(kb_session* s, int32_t task_id, int32_t* out_node, int64_t* out_delta, int64_t cap);
+
 int kbhip_session_close(kb_session* s);
 
 /* Node-array sharding (one process per GPU).  A shard session
@@ -463,6 +509,10 @@ int kbhip_shard_connect_host_gather(kb_session* s, kbhip_allgather_fn fn, void* 
  *                upd_off, upd_n, score_err, 0
  *   "aff_dom"    [n_spaces][npad] topology domain ids
  *   "aff_cnt", "aff_scalar", "aff_items"  pod-affinity count tables / programs
+ *   "node_idle", "node_backfilled"  (encode-only sessions) int64 [n_nodes][3]:
+ *                cpu, memory, GPU of the host tables kbhip_debug_replay mutates
+ *   "node_visits"  (encode-only sessions) uint32 [n_nodes]: the walk visit
+ *                counters of kbhip_walk_visits as the replay counts them
  * kbhip_debug_table returns the table size in bytes and copies it when
  * cap_bytes is large enough.  Sessions from kbhip_debug_encode reject every
  * call that needs a device (KBHIP_EINVAL). */

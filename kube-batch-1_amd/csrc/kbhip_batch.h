@@ -1139,6 +1139,7 @@ __device__ void place_bf(const Conf& cf, const NodeCols& nc, const DevTables& t,
     uint64_t key = n >= 0 ? dyn_key(cf, c, t, nc, r, pw, n, true, na_n, &s, &passed) : 0;
     uint64_t wk = (n >= 0 && passed) ? pack_key(s, n, 0) >> 1 : 0;  // walk key (0: not in the walk)
     bool changed = false;
+    uint32_t visits = 0;  // this lane's node: visits by the pop's walks (kbhip_walk_visits)
     int ready = a.ready_count, done = 0, stop = 0;
     uint64_t mine = 0;  // lane i: winner key of task i
     for (int i = 0; i < a.n_tasks; ++i) {
@@ -1147,7 +1148,7 @@ __device__ void place_bf(const Conf& cf, const NodeCols& nc, const DevTables& t,
         if (lane == i) mine = w;
         const bool win = n >= 0 && key == w;
         const bool visit = has_bf && (win || wk > (w >> 1));
-        if (visit) { r.idle_cpu += r.bf_cpu; r.idle_mem += r.bf_mem; r.idle_gpu += r.bf_gpu; }
+        if (visit) { r.idle_cpu += r.bf_cpu; r.idle_mem += r.bf_mem; r.idle_gpu += r.bf_gpu; ++visits; }
         const int kind = key_kind(w);
         if (win) {
             r = apply_commits(r, c, kind == 1 ? 1 : 0, kind == 1 ? 0 : 1);
@@ -1171,6 +1172,7 @@ __device__ void place_bf(const Conf& cf, const NodeCols& nc, const DevTables& t,
         nc.nzm[n] = r.nzm;
         if (c.has_ports)
             for (int w = 0; w < 4; ++w) if (w < port_win(c, nc)) nc.ports[port_at(c, nc, w, n)] = pw[w];
+        if (visits) nc.visits[n] += visits;
     }
     if (lane < done || (done == 0 && lane == 0))
         __hip_atomic_store(&out->g[lane],

@@ -54,6 +54,26 @@ hipError_t launch_evict_read(const void* buf, size_t bytes, hipStream_t st);  //
 void set_sweep_variant(int v);  // option "sweep_variant" (process-wide tuning knob)
 hipError_t launch_score_sweep(const Conf& cf, const NodeCols& nc, const DevTables& t, const TaskClass& c,
                               const PopCtrl* ctrl, uint64_t* keys, uint32_t* counts, hipStream_t st);
+// Walk read-outs (kbhip_walk.hip): ordered stream compaction over the node
+// columns in three launches.  mark: one ballot word per wave (mask, 4 per
+// block of kBlock nodes) and the block's count (blk[b]); scan: blk[0 .. nb)
+// becomes the exclusive prefix sum and blk[nb] the total; scatter: record i of
+// the ascending node order lands at index i.  compact_blocks(n) = nb.
+int compact_blocks(int n_nodes);
+// mark of kbhip_fit_deltas: the nodes the walk of the task of class c visits
+// (PredicateFn passes and NodeOrderFn scores: the walk's own eval_node /
+// eval_node_aff, ctrl task 0 holding the inter-pod prepass and fallback node)
+hipError_t launch_fit_mark(const Conf& cf, const NodeCols& nc, const DevTables& t, const TaskClass& c,
+                           const PopCtrl* ctrl, uint64_t* mask, uint32_t* blk, hipStream_t st);
+// mark of kbhip_walk_visits: nodes with a non-zero visit counter
+hipError_t launch_visit_mark(const NodeCols& nc, uint64_t* mask, uint32_t* blk, hipStream_t st);
+hipError_t launch_compact_scan(uint32_t* blk, int nb, hipStream_t st);
+// out_delta[3 i ..]: Idle.FitDelta(Resreq) of record i's node (resource_info.go:134-147)
+hipError_t launch_fit_scatter(const NodeCols& nc, const TaskClass& c, const uint64_t* mask, const uint32_t* blk,
+                              int32_t* out_node, int64_t* out_delta, hipStream_t st);
+// out_count[i]: the node's counter, cleared when clear != 0
+hipError_t launch_visit_scatter(const NodeCols& nc, const uint64_t* mask, const uint32_t* blk, int32_t* out_node,
+                                uint32_t* out_count, int clear, hipStream_t st);
 hipError_t launch_rank_nodes(const Conf& cf, const NodeCols& nc, const DevTables& t, const PopCtrl* ctrl,
                              int by_score, uint64_t* keys, uint32_t* count, hipStream_t st);
 // Wide score ranges: the passing keys of launch_rank_nodes (n keys, zeros

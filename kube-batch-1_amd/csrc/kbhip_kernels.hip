@@ -167,6 +167,7 @@ __device__ void commit_task(const NodeCols& nc, const DevTables& t, PopCtrl* ctr
             if (own) {
                 if (track) {  // the winner is visited too: Idle += Backfilled first (node_info.go:209-211)
                     nc.idle_cpu[n] += nc.bf_cpu[n]; nc.idle_mem[n] += nc.bf_mem[n]; nc.idle_gpu[n] += nc.bf_gpu[n];
+                    if (nc.bf_cpu[n] | nc.bf_mem[n] | nc.bf_gpu[n]) nc.visits[n] += 1;  // kbhip_walk_visits
                 }
                 commit_node(c, t, nc, n, kind);
             }
@@ -204,6 +205,7 @@ __device__ void commit_task(const NodeCols& nc, const DevTables& t, PopCtrl* ctr
         if (!v || n + nc.base == wn) continue;
         if (k && v < wk) continue;
         nc.idle_cpu[n] += nc.bf_cpu[n]; nc.idle_mem[n] += nc.bf_mem[n]; nc.idle_gpu[n] += nc.bf_gpu[n];
+        if (nc.bf_cpu[n] | nc.bf_mem[n] | nc.bf_gpu[n]) nc.visits[n] += 1;  // kbhip_walk_visits
     }
 }
 
@@ -292,6 +294,7 @@ __device__ __forceinline__ void visit_body(const NodeCols& nc, const PopCtrl* ct
         if (!v || n + nc.base == wn) continue;
         if (k && v < wk) continue;
         nc.idle_cpu[n] += nc.bf_cpu[n]; nc.idle_mem[n] += nc.bf_mem[n]; nc.idle_gpu[n] += nc.bf_gpu[n];
+        if (nc.bf_cpu[n] | nc.bf_mem[n] | nc.bf_gpu[n]) nc.visits[n] += 1;  // kbhip_walk_visits
     }
 }
 __global__ __launch_bounds__(kBlock) void k_visit_mutate(NodeCols nc, const PopCtrl* ctrl, int task_i,

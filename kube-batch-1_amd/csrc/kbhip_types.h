@@ -28,6 +28,8 @@ struct NodeCols {
     int64_t *nzc, *nzm;                        // k8s NodeInfo.nonzeroRequest
     int32_t *pods, *maxtasks;                  // len(node.Pods()), Allocatable.MaxTaskNum
     uint8_t *flags;                            // bit0: Spec.Unschedulable
+    uint32_t *visits;                          // nodes with Backfilled != 0: GetAccessibleResource calls of allocate
+                                               // walks since the last kbhip_walk_visits (each added Backfilled to Idle)
     int32_t *labels;                           // [n_keys][npad]
     uint64_t *taints;                          // [taint_words][npad] NoSchedule/NoExecute taint ids
     uint64_t *ports;                           // [port_words][npad] used (ip, proto, port) ids

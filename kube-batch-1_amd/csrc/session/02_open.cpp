@@ -1094,6 +1094,8 @@ void open_session(Session& S, const kbs::Snapshot& s, int device, bool encode_on
     S.nc.pods = upload(S, S.b_cols[13], pods_col);
     S.nc.maxtasks = upload(S, S.b_cols[14], max_col);
     S.nc.flags = upload(S, S.b_cols[15], flags_col);
+    S.nc.visits = S.b_cols[16].alloc<uint32_t>(npl, encode_only);  // kbhip_walk_visits: zero at open (host: calloc)
+    if (!encode_only) HIPCHK(hipMemsetAsync(S.nc.visits, 0, (size_t)npl * sizeof(uint32_t), S.stream));
     const int K = (int)E.sel_keys.size();
     vector<int32_t> lab((size_t)std::max(K, 1) * npl, -1);
     for (auto& kv : E.sel_keys) {

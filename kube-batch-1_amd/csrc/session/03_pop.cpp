@@ -899,6 +899,7 @@ int place_job(Session& S, const int32_t* ids, int n, int gang_mode, int min_avai
                      int32_t* out_node, uint8_t* out_kind, int32_t* out_n_done, int32_t* out_stop) {
     int done = 0, stop = KBHIP_STOP_ALL;
     check_task_ids(S, ids, n);
+    S.fit_task = -1;
     while (done < n) {
         const int cls0 = S.pods[ids[done]].cls;
         int m = 1;
@@ -997,6 +998,7 @@ int place_job(Session& S, const int32_t* ids, int n, int gang_mode, int min_avai
     }
     *out_n_done = done;
     *out_stop = stop;
+    if (stop == KBHIP_STOP_UNASSIGNED && done >= 1) S.fit_task = ids[done - 1];  // kbhip_fit_deltas
     return 0;
 }
 
@@ -1107,6 +1109,7 @@ int place_job_wait(Session& S, int64_t ticket, int32_t* out_node, uint8_t* out_k
     }
     PopTicket t = std::move(S.tickets.front());
     S.tickets.pop_front();
+    S.fit_task = -1;
     const int n = (int)t.ids.size();
     bool sync = !t.collected;
     if (t.collected) {
@@ -1121,6 +1124,7 @@ int place_job_wait(Session& S, int64_t ticket, int32_t* out_node, uint8_t* out_k
             apply_results(S, t.ids.data(), nd, S.res_node_buf, S.res_kind_buf, out_node, out_kind);
             *out_n_done = nd;
             *out_stop = st;
+            if (st == KBHIP_STOP_UNASSIGNED) S.fit_task = t.ids[nd - 1];  // kbhip_fit_deltas
             if (st == KBHIP_STOP_ALL && nd < n) {
                 // the launch ended before its chunk did (a sequential placement whose list ran out): the
                 // pop goes on with its remaining tasks (allocate.go:110-196), synchronously; the launches

@@ -740,6 +740,7 @@ struct Allocator {
                 okind.assign(n, 0);
                 int32_t n_done = 0, stop = 0;
                 exec_pop(q, jb, n, &n_done, &stop);
+                S.fit_task = (stop == KBHIP_STOP_UNASSIGNED && n_done >= 1) ? ids[n_done - 1] : -1;  // kbhip_fit_deltas
                 S.stats.tasks += n_done;
                 for (int i = 0; i < n_done; ++i) {
                     const int pi = ids[i];
@@ -1468,10 +1469,12 @@ struct Allocator {
 // The actions other files run (05_actions.cpp, 06_carry.cpp): the allocate
 // action, reclaim / preempt, and the first-fit node loop of given tasks.
 void allocate_run(Session& S) {
+    S.fit_task = -1;
     Allocator a(S);
     a.run();
 }
 void evict_run(Session& S, bool preempt) {
+    S.fit_task = -1;
     Allocator a(S);
     if (preempt) a.preempt_action();
     else a.reclaim_action();
@@ -1494,6 +1497,7 @@ void first_fit(Session& S, const int32_t* ids, int n, int32_t* out_node) {
         if (t < 0 || t >= (int)S.pods.size() || S.pods[t].cls < 0 || S.pods[t].status != Pending)
             throw Error(KBHIP_EINVAL, "task id is not a pending task of the session");
     std::fill(out_node, out_node + n, -1);
+    S.fit_task = -1;
     ov_quiesce(S);
     Allocator A(S);
     A.compile_orders();

@@ -408,6 +408,8 @@ void session_carry(Session& S, const int32_t* ev_pod, const uint8_t* ev, int64_t
         }
     };
     for (int k = 0; k < 9; ++k) sync_col(dcol[k], col[k].data() + lo, sizeof(int64_t));
+    HIPCHK(hipMemsetAsync(S.nc.visits, 0, (size_t)S.nc.npad * sizeof(uint32_t), S.stream));  // a new session's walks
+    S.fit_task = -1;
     sync_col(S.nc.pods, podcnt.data() + lo, sizeof(int32_t));
     sync_col(S.nc.nzc, nzc.data() + lo, sizeof(int64_t));
     sync_col(S.nc.nzm, nzm.data() + lo, sizeof(int64_t));

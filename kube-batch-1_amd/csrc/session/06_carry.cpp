@@ -699,6 +699,8 @@ void carry_snapshot(kb_session* ks, const kbs::Snapshot& s, const int32_t* old_p
         else scan(uint8_t{0});
     };
     for (int k = 0; k < 13; ++k) sync_col(dcol[k], col[k].data(), sizeof(int64_t));
+    HIPCHK(hipMemsetAsync(S.nc.visits, 0, (size_t)S.nc.npad * sizeof(uint32_t), S.stream));  // a new session's walks
+    S.fit_task = -1;
     sync_col(S.nc.pods, podcnt.data(), sizeof(int32_t));
     sync_col(S.nc.maxtasks, maxc.data(), sizeof(int32_t));
     sync_col(S.nc.flags, flg.data(), sizeof(uint8_t));

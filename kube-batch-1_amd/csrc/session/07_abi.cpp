@@ -450,6 +450,24 @@ int64_t kbhip_debug_table(kb_session* s, const char* name, void* out, int64_t ca
             const int64_t bytes = (int64_t)(S.dbg_keys.size() * 8);
             if (out && cap_bytes >= bytes && bytes) std::memcpy(out, S.dbg_keys.data(), (size_t)bytes);
             return bytes;
+        } else if (n == "node_idle" || n == "node_backfilled" || n == "node_visits") {
+            // encode-only sessions (kbhip_debug_replay's host restatement): Idle / Backfilled as int64
+            // [n_nodes][3] (cpu, memory, GPU), the walk visit counters as uint32 [n_nodes]
+            if (!S.encode_only) throw kbhip::Error(KBHIP_EINVAL, "node tables are read from encode-only sessions");
+            const int64_t N = S.nc.n;
+            if (n == "node_visits") {
+                const int64_t bytes = N * (int64_t)sizeof(uint32_t);
+                if (out && cap_bytes >= bytes && bytes) std::memcpy(out, S.nc.visits, (size_t)bytes);
+                return bytes;
+            }
+            const bool idle = n == "node_idle";
+            const int64_t* col[3] = {idle ? S.nc.idle_cpu : S.nc.bf_cpu, idle ? S.nc.idle_mem : S.nc.bf_mem,
+                                     idle ? S.nc.idle_gpu : S.nc.bf_gpu};
+            const int64_t bytes = N * 3 * (int64_t)sizeof(int64_t);
+            if (out && cap_bytes >= bytes)
+                for (int64_t i = 0; i < N; ++i)
+                    for (int k = 0; k < 3; ++k) ((int64_t*)out)[3 * i + k] = col[k][i];
+            return bytes;
         } else if (n == "dbg_pods") {
             v = S.dbg_pods;
         } else if (n == "engine_tl") {  // u64 words: kEngTlSlots x kEngTlEvents (option "engine_timeline")
@@ -516,6 +534,7 @@ int kbhip_debug_replay(kb_session* s, int32_t n_steps, const int32_t* pods, cons
                 const int kind = first_fit ? 1 : kinds[i];
                 if (track) {
                     nc.idle_cpu[w] += nc.bf_cpu[w]; nc.idle_mem[w] += nc.bf_mem[w]; nc.idle_gpu[w] += nc.bf_gpu[w];
+                    if (nc.bf_cpu[w] | nc.bf_mem[w] | nc.bf_gpu[w]) nc.visits[w] += 1;
                 }
                 commit_node(c, t, nc, w, kind);
                 if (c.aff) commit_aff(c, t, nc, w, kind);
@@ -528,6 +547,7 @@ int kbhip_debug_replay(kb_session* s, int32_t n_steps, const int32_t* pods, cons
                     if (!walk[n] || n == w) continue;
                     if (k && walk[n] < wk) continue;
                     nc.idle_cpu[n] += nc.bf_cpu[n]; nc.idle_mem[n] += nc.bf_mem[n]; nc.idle_gpu[n] += nc.bf_gpu[n];
+                    if (nc.bf_cpu[n] | nc.bf_mem[n] | nc.bf_gpu[n]) nc.visits[n] += 1;
                 }
             }
         }

@@ -683,6 +683,13 @@ struct Session {
     bool last_fit_ok = false;            // ... computed in-kernel (else: fit_sync)
     DevBuf b_fit4;
     int32_t* d_fit4 = nullptr;
+    // kbhip_fit_deltas: the task on which the session's most recent pop stopped unassigned (-1: the last
+    // pop ended otherwise, or a later call changed the state) — nothing was committed after that task's
+    // walk, so the node columns are still the ones it saw
+    int32_t fit_task = -1;
+    // kbhip_walk_visits / kbhip_fit_deltas: the compaction's ballot words and block offsets, its records
+    DevBuf b_cmp_mask, b_cmp_blk, b_cmp_node, b_cmp_val;
+    size_t cmp_blocks = 0, cmp_node_n = 0, cmp_val_bytes = 0;
     vector<string> job_uid;              // by job slot (UID order)
     bool gang_close = false;             // the gang plugin is in the tiers (its OnSessionClose reports)
     uint8_t fit_set[kMaxDep + 2] = {};   // FitDelta counter set of the next launch, per stream (last: k_pop_batch)
@@ -833,7 +840,8 @@ struct Session {
                           &b_masks, &b_ctrl, &b_walk, &b_dom, &b_aff_items, &b_aff_cnt, &b_aff_scalar, &b_cand2,
                           &b_arrive, &b_link, &b_dbg, &b_fit4, &b_rank_keys, &b_rank_sorted, &b_rank_tmp, &b_rank_cnt,
                           &b_rank_radix,
-                          &b_shard_send, &b_shard_recv, &b_tab_idx, &b_sweep_cnt, &b_dd_max})
+                          &b_shard_send, &b_shard_recv, &b_tab_idx, &b_sweep_cnt, &b_dd_max, &b_cmp_mask, &b_cmp_blk,
+                          &b_cmp_node, &b_cmp_val})
             b->release();
         for (auto& b : b_cand_ov) b.release();
         for (auto& b : b_arrive_ov) b.release();
@@ -1141,6 +1149,8 @@ void sweep_task(Session& S, int i, int cls, bool defer_visits = false);
 void rank_buffers(Session& S);
 void backfill_run(Session& S);
 int sweep_scores(Session& S, int pod, uint64_t* out_keys);
+int64_t walk_visits(Session& S, int32_t* out_node, uint32_t* out_count, int64_t cap);
+int64_t fit_deltas(Session& S, int pod, int32_t* out_node, int64_t* out_delta, int64_t cap);
 double time_sweeps(Session& S, const int32_t* ids, int n);
 double time_rank_multi(Session* const* ss, int n, const int32_t* ids, int reps, int evict, int mapped);
 string fit_error(const HJob& j);

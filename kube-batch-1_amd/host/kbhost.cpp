@@ -10,6 +10,7 @@
 //
 // Two ways to drive the engine:
 //   sync   one kbhip_place_job call per pop (a round trip per pop);
+//   walk   sync plus the walk read-outs after each pop (kbhip_walk_visits, kbhip_fit_deltas);
 //   async  kbhip_place_job_submit / _wait / _cancel: while pop e runs the
 //          host predicts the next `depth` pops (assuming each places its tasks
 //          as Allocated up to the gang stop) on its own model — every change
@@ -487,7 +488,39 @@ struct Host {
     const int32_t* ids(const Pop& p) const { return jobs[p.k].pending.data() + p.cursor; }
     int n_ids(const Pop& p) const { return (int)jobs[p.k].pending.size() - p.cursor; }
 
-    void run_sync(kb_session* s) {
+    // Mode "walk": the synchronous loop with the walk read-outs a Go host needs to keep the
+    // reference's own NodeInfo / JobInfo exact (go/kbhip/allocate_hip.go): after every pop the
+    // nodes its walks visited (node.GetAccessibleResource() `count` times each, before the pop's
+    // placements are applied), and after a pop that stopped unassigned the NodesFitDelta records
+    // of its last task.  Both need a quiescent session, so the pipelined loop does not call them.
+    int64_t visit_nodes = 0, visit_sum = 0, fit_pops = 0, fit_records = 0;
+    vector<int32_t> rd_node;
+    vector<uint32_t> rd_count;
+    vector<int64_t> rd_delta;
+    void read_walk(kb_session* s, int32_t last_task, int stop) {
+        int64_t n = kbhip_walk_visits(s, nullptr, nullptr, 0);
+        check((int)std::max<int64_t>(n, -100), "kbhip_walk_visits");
+        if (n > 0) {
+            rd_node.resize(n);
+            rd_count.resize(n);
+            check((int)std::max<int64_t>(kbhip_walk_visits(s, rd_node.data(), rd_count.data(), n), -100),
+                  "kbhip_walk_visits");
+            visit_nodes += n;
+            for (int64_t i = 0; i < n; ++i) visit_sum += rd_count[i];  // Idle += count x Backfilled on rd_node[i]
+        }
+        if (stop != KBHIP_STOP_UNASSIGNED) return;
+        n = kbhip_fit_deltas(s, last_task, nullptr, nullptr, 0);
+        check((int)std::max<int64_t>(n, -100), "kbhip_fit_deltas");
+        rd_node.resize(std::max<int64_t>(n, 1));
+        rd_delta.resize(3 * std::max<int64_t>(n, 1));
+        if (n > 0)
+            check((int)std::max<int64_t>(kbhip_fit_deltas(s, last_task, rd_node.data(), rd_delta.data(), n), -100),
+                  "kbhip_fit_deltas");
+        ++fit_pops;
+        fit_records += n;  // job.NodesFitDelta = {rd_node[i]: rd_delta[3 i ..]} (replaces the job's map)
+    }
+
+    void run_sync(kb_session* s, bool walk = false) {
         start();
         vector<int32_t> node;
         vector<uint8_t> kind;
@@ -501,6 +534,7 @@ struct Host {
             check(kbhip_place_job(s, ids(p), n, gang_ready, jobs[p.k].min, p.ready, node.data(), kind.data(), &nd,
                                   &stop),
                   "kbhip_place_job");
+            if (walk && nd > 0) read_walk(s, ids(p)[nd - 1], stop);
             apply(p, nd, node.data(), kind.data(), stop, true);
         }
     }
@@ -641,15 +675,20 @@ int main(int argc, char** argv) {
                     t_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
                     check(n, "kbhip_allocate");
                     for (int i = 0; i < n; ++i) log.push_back(Rec{pod[i], node[i], kind[i] == KBHIP_ALLOCATED ? 4 : 8});
-                } else if (m == "sync" || m == "async") {
+                } else if (m == "sync" || m == "async" || m == "walk") {
                     Host h(snap);
                     const auto t0 = std::chrono::steady_clock::now();
-                    if (m == "sync") h.run_sync(s);
+                    if (m == "sync" || m == "walk") h.run_sync(s, m == "walk");
                     else h.run_async(s, depth);
                     t_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
                     log.swap(h.log);
                     pops = h.pops;
                     misses = h.misses;
+                    if (m == "walk")
+                        std::fprintf(stderr, "kbhost walk: %lld visited nodes (%lld visits), %lld unassigned pops "
+                                             "with %lld FitDelta records\n",
+                                     (long long)h.visit_nodes, (long long)h.visit_sum, (long long)h.fit_pops,
+                                     (long long)h.fit_records);
                 } else {
                     throw std::runtime_error("unknown mode " + m);
                 }

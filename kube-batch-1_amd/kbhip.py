@@ -31,7 +31,7 @@ EXPORTS = ("kbhip_device_count", "kbhip_session_open", "kbhip_session_open_file"
            "kbhip_first_fit", "kbhip_sweep_scores", "kbhip_shard_connect_host_gather",
            "kbhip_session_carry_events", "kbhip_shard_connect_mailbox", "kbhip_shard_mailbox_fits", "kbhip_place_job_submit",
            "kbhip_place_job_wait", "kbhip_place_job_cancel", "kbhip_time_sweeps", "kbhip_time_rank_multi",
-           "kbhip_session_carry_snapshot")
+           "kbhip_session_carry_snapshot", "kbhip_walk_visits", "kbhip_fit_deltas")
 
 RED_MAX_U64, RED_MIN_I64, RED_MAX_I64, RED_SUM_I64 = 0, 1, 2, 3
 ALLREDUCE_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint64), ctypes.c_int32,
@@ -124,6 +124,10 @@ def lib() -> ctypes.CDLL:
         L.kbhip_gang_unschedulable.argtypes = [vp, ctypes.c_char_p, i64]
         L.kbhip_gang_unschedulable.restype = i64
         L.kbhip_debug_replay.argtypes = [vp, i32, vp, vp, vp, vp, vp]
+        L.kbhip_walk_visits.argtypes = [vp, vp, vp, i64]
+        L.kbhip_walk_visits.restype = i64
+        L.kbhip_fit_deltas.argtypes = [vp, i32, vp, vp, i64]
+        L.kbhip_fit_deltas.restype = i64
         _lib = L
     return _lib
 
@@ -331,6 +335,34 @@ class Session:
         _check(lib().kbhip_read_nodes(self._h, _p(out), n_nodes))
         return out
 
+    def walk_visits(self) -> Tuple[np.ndarray, np.ndarray]:
+        """kbhip_walk_visits: (node, count) of the nodes allocate walks visited
+        since the previous call (GetAccessibleResource calls: each added the
+        node's Backfilled to its Idle), ascending node index; clears them."""
+        n = int(lib().kbhip_walk_visits(self._h, None, None, 0))
+        _check(n if n < 0 else 0)
+        node = np.zeros(max(n, 1), np.int32)
+        cnt = np.zeros(max(n, 1), np.uint32)
+        if n:
+            m = int(lib().kbhip_walk_visits(self._h, _p(node), _p(cnt), n))
+            _check(m if m < 0 else 0)
+            if m != n:
+                raise KbhipError("kbhip_walk_visits: the count changed between the size query and the read")
+        return node[:n].copy(), cnt[:n].copy()
+
+    def fit_deltas(self, task_id: int) -> Tuple[np.ndarray, np.ndarray]:
+        """kbhip_fit_deltas: job.NodesFitDelta of the task on which the most
+        recent pop stopped unassigned: (node [k], delta [k, 3] = cpu, memory,
+        GPU), ascending node index."""
+        n = int(lib().kbhip_fit_deltas(self._h, int(task_id), None, None, 0))
+        _check(n if n < 0 else 0)
+        node = np.zeros(max(n, 1), np.int32)
+        delta = np.zeros((max(n, 1), 3), np.int64)
+        if n:
+            m = int(lib().kbhip_fit_deltas(self._h, int(task_id), _p(node), _p(delta), n))
+            _check(m if m < 0 else 0)
+        return node[:n].copy(), delta[:n].copy()
+
     def debug_keys(self) -> Tuple[np.ndarray, np.ndarray]:
         """Test support (after set_option("debug_keys", 1) and a run): the pod of
         every per-task sweep and its row: per-node keys, per-node raw inter-pod
@@ -395,6 +427,15 @@ class EncodedSnapshot:
         out = np.zeros(max(int(n) // 4, 1), np.int32)
         _check(int(lib().kbhip_debug_table(self._h, name.encode(), _p(out), out.nbytes)) if n > 0 else 0)
         return out[: int(n) // 4]
+
+    def table_raw(self, name: str, dtype) -> np.ndarray:
+        """A table of another element type (node_idle / node_backfilled: int64, node_visits: uint32)."""
+        n = int(lib().kbhip_debug_table(self._h, name.encode(), None, 0))
+        _check(n if n < 0 else 0)
+        out = np.zeros(max(n // np.dtype(dtype).itemsize, 1), dtype)
+        if n:
+            _check(int(lib().kbhip_debug_table(self._h, name.encode(), _p(out), out.nbytes)))
+        return out[: n // np.dtype(dtype).itemsize]
 
     def replay(self, pods, modes, nodes, kinds) -> np.ndarray:
         """Per-step, per-node selection keys along a given decision sequence
