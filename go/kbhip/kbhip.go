@@ -216,6 +216,38 @@ func (e *Engine) FitDeltas(task int32) ([]FitDelta, error) {
 	return out, nil
 }
 
+// RankNodes returns entries [first, first+n) of the ranked node walk of a
+// Pending task (kbhip_rank_nodes) and the walk's length: byScore true is
+// preempt()'s walk (preempt.go:270-287: the nodes passing PredicateFn with a
+// NodeOrderFn score, in util.SelectBestNode order), false reclaim's (the
+// passing nodes in index order, scores 0).  first+n <= 64 is served by the
+// top-64 kernel, any other window by the full device sort; n = 0 asks for the
+// length alone.  The session state is not changed.
+func (e *Engine) RankNodes(task int32, byScore bool, first, n int64) (total int64, nodes, scores []int32, err error) {
+	if n < 0 || first < 0 {
+		return 0, nil, nil, fmt.Errorf("kbhip rank_nodes: negative window")
+	}
+	var pn, ps *C.int32_t
+	if n > 0 { // &nodes[0] of an empty slice panics
+		nodes = make([]int32, n)
+		scores = make([]int32, n)
+		pn = (*C.int32_t)(unsafe.Pointer(&nodes[0]))
+		ps = (*C.int32_t)(unsafe.Pointer(&scores[0]))
+	}
+	t := C.kbhip_rank_nodes(e.s, C.int32_t(task), boolI32(byScore), C.int64_t(first), pn, ps, C.int64_t(n))
+	if t < 0 {
+		return 0, nil, nil, lastErr("rank_nodes", C.int(t))
+	}
+	got := int64(t) - first
+	if got < 0 {
+		got = 0
+	}
+	if got > n {
+		got = n
+	}
+	return int64(t), nodes[:got], scores[:got], nil
+}
+
 // GangUnschedulable is the gang plugin's OnSessionClose text after Allocate
 // (gang.go:166-187): "<job uid>\t<message>\n" per job that is not ready.
 func (e *Engine) GangUnschedulable() (string, error) {

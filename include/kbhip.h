@@ -128,6 +128,8 @@ typedef struct kbhip_stats {
     int64_t engine_owners;   /* list mode (option "engine_lists"): its class-owner blocks (0: sweep mode) */
     int64_t engine_not_resident; /* engine grids that could not become resident (other kernels held CUs)
                                     and were started again */
+    int64_t rank_heads;      /* kbhip_rank_nodes calls served by the top-64 kernel (first + cap <= 64) */
+    int64_t rank_fulls;      /* ... served by the full device sort */
 } kbhip_stats;
 
 /* Library / device probe: returns the number of usable gfx950 devices (>= 0),
@@ -211,9 +213,38 @@ int kbhip_backfill(kb_session* s, int32_t* out_pod, int32_t* out_node, uint8_t* 
  *   biased by 2^31, (0x7fffffff - n) << 1 below — for a node that passes
  *   PredicateFn and has a NodeOrderFn score, 0 otherwise; sorting the keys
  *   descending is util.SelectBestNode's order (util/sort.go:25-37).  The
- *   session state is not changed.  Returns the number of passing nodes. */
+ *   session state is not changed.  Returns the number of passing nodes.
+ * kbhip_rank_nodes <- the node walk of preempt() and of reclaim, ranked on
+ *   the device, for a host that keeps the loop over the nodes itself:
+ *     by_score 1  the nodes that pass PredicateFn and have a NodeOrderFn
+ *                 score, in util.SelectBestNode order (preempt.go:270-287):
+ *                 kbhip_sweep_scores' keys sorted descending, so equal scores
+ *                 go to the lower node index;
+ *     by_score 0  the nodes that pass PredicateFn, in ascending index (the
+ *                 node loop of reclaim.go).
+ *   Returns the number T of such nodes and writes entries [first, min(T,
+ *   first + cap)) of the walk: out_node[i] = the node index, out_score[i]
+ *   (optional) = its NodeOrderFn score (0 with by_score 0).  cap 0 with null
+ *   outputs is the size query.  A request with first + cap <= 64 and cap > 0
+ *   (the head of the walk, where preempt and reclaim usually stop) is served
+ *   by one fused predicate + score + top-64 selection sweep: no per-node array
+ *   is written and 64 keys plus the count are copied back.  Every other
+ *   request runs the full device sort the reclaim / preempt actions use (a
+ *   counting sort over the class's score range, or the radix passes: option
+ *   "rank_radix") and copies only the entries asked for.  Nothing is kept
+ *   between calls: a host that wants the head and then the rest calls twice.
+ *   Like kbhip_sweep_scores the call reads the session state and changes
+ *   nothing: no node row, no counter of kbhip_walk_visits, and a task
+ *   kbhip_fit_deltas would answer for stays answerable.  KBHIP_EINVAL: a null
+ *   session, a task without a task class (not a pending task of the session)
+ *   or one the session's own actions have placed since, first < 0, cap < 0, cap > 0 with a null out_node, by_score other than 0
+ *   or 1, an encode-only session, submitted pops outstanding;
+ *   KBHIP_EUNSUPPORTED on node-sharded sessions (as kbhip_sweep_scores);
+ *   KBHIP_EDEVICE when the full sort met a score outside the class's range. */
 int kbhip_first_fit(kb_session* s, const int32_t* task_ids, int32_t n, int32_t* out_node);
 int kbhip_sweep_scores(kb_session* s, int32_t task_id, uint64_t* out_keys);
+int64_t kbhip_rank_nodes(kb_session* s, int32_t task_id, int32_t by_score, int64_t first, int32_t* out_node,
+                         int32_t* out_score, int64_t cap);
 
 /* Measurement hook (bench.py's sweep roofline): kbhip_sweep_scores' sweep
  * kernel for each given task, launched back to back on the session stream

@@ -20,6 +20,7 @@
 // sweep does not use) + 8 B written per node + the sort's passes over 8 B keys.
 #include <hip/hip_runtime.h>
 
+#include "kbhip_batch.h"
 #include "kbhip_eval.h"
 #include "kbhip_internal.h"
 
@@ -578,6 +579,152 @@ hipError_t launch_rank_sorted_multi(const RankDesc* d_desc, int n_desc, int max_
     return hipGetLastError();
 }
 size_t rank_hist_words(int n_nodes) { return (size_t)kRankBuckets * ((n_nodes + kBlock - 1) / kBlock + 1); }
+
+// ---------------------------------------------------------------------------
+// The head of a walk (kbhip_rank_nodes with first + cap <= kTopK): the best
+// kTopK keys of the order above and the passing count, with no per-node array
+// written.  The walks of preempt and reclaim usually stop within their first
+// few nodes; the head is what such a host asks for first.
+//   k_rank_head        the sweep.  A wave takes 64 consecutive nodes per step
+//                      (lane = node, loads coalesced), evaluates PredicateFn +
+//                      NodeOrderFn into pack_key(score, index) (by_score 0:
+//                      the predicates alone, score 0 — the order is the index),
+//                      sorts the 64 keys in registers (wave_sort_desc) and
+//                      merges them into its running top 64 (wave_merge_desc); a
+//                      step none of whose keys beats the wave's 64th is not
+//                      merged.  The block's waves merge through LDS; one sorted
+//                      list of 64 keys and the block's passing count go out.
+//                      Grid: at most one block per CU (rank_head_blocks), the
+//                      steps beyond it grid-strided, a plain class's columns
+//                      of the next step loaded before the current one is
+//                      evaluated (as k_score_sweep_gs).
+//   k_rank_head_merge  one block: wave w merges block lists w, w + 4, ...,
+//                      the four results merge through LDS; out[0 .. 63] = the
+//                      keys (descending, 0 beyond the passing count), out[64] =
+//                      the passing count.
+// The launch boundary orders the two kernels: no block waits for another.
+// Traffic per node: the 41 B of columns of the sweep above (eval_node_aff's
+// classes: the whole row), nothing written; per block 516 B out.
+// ---------------------------------------------------------------------------
+constexpr int kHeadWaves = kBlock / 64;
+constexpr int kHeadMaxBlocks = 1024;  // scratch size (rank_head_words); the grid is capped at the CU count below it
+
+// The waves' sorted lists merged into s_top[0] (every wave of the block calls).
+__device__ __forceinline__ void head_block_merge(uint64_t (*s_top)[64], uint64_t top, int wave, int lane) {
+    s_top[wave][lane] = top;
+    __syncthreads();
+#pragma unroll
+    for (int s = kHeadWaves / 2; s >= 1; s >>= 1) {
+        if (wave < s) s_top[wave][lane] = wave_merge_desc(s_top[wave][lane], s_top[wave + s][lane]);
+        __syncthreads();
+    }
+}
+
+template <bool PLAIN>
+__global__ __launch_bounds__(kBlock) void k_rank_head(Conf cf, NodeCols nc, DevTables t, TaskClass c,
+                                                      const PopCtrl* ctrl, int by_score, uint64_t* lists,
+                                                      uint32_t* bcnt) {
+    __shared__ uint64_t s_top[kHeadWaves][64];
+    __shared__ uint32_t s_cnt[kHeadWaves];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int stride = gridDim.x * kBlock;
+    uint64_t top = 0;  // lane i: the wave's i-th best key so far
+    uint32_t cnt = 0;  // passing nodes of the wave (uniform)
+    // b is the wave's first node of the step: uniform, so every lane runs the
+    // sort and merge networks (lanes past the last node hold key 0)
+    int b = blockIdx.x * kBlock + wave * 64;
+    SweepIn cur{};
+    if (PLAIN && b + lane < nc.n) cur = sweep_in(nc, b + lane);
+    for (; b < nc.n; b += stride) {
+        const int n = b + lane;
+        uint64_t k = 0;
+        if constexpr (PLAIN) {
+            SweepIn nxt{};
+            if (n + stride < nc.n) nxt = sweep_in(nc, n + stride);
+            if (n < nc.n) {
+                uint64_t pw[4] = {0, 0, 0, 0};
+                if (c.has_ports)
+                    for (int w = 0; w < 4; ++w) if (w < port_win(c, nc)) pw[w] = nc.ports[port_at(c, nc, w, n)];
+                Row r{};
+                r.acpu = cur.acpu; r.amem = cur.amem; r.nzc = cur.nzc; r.nzm = cur.nzm;
+                r.pods = cur.pods; r.maxtasks = cur.maxtasks;
+                const bool st = static_pred_f(cf, c, t, nc, n, cur.fl);
+                const int32_t na = (st && cf.score_mult) ? na_weight(c, t, nc, n) : 0;
+                int32_t s = 0;
+                bool passed = false;
+                (void)dyn_key(cf, c, t, nc, r, pw, n, st, na, &s, &passed);  // passed and s read no fit column
+                k = passed ? pack_key(s, n + nc.base, 0) : 0;
+            }
+            cur = nxt;
+        } else if (n < nc.n) {
+            if (by_score) {
+                int32_t s = 0;
+                bool passed = false;
+                (void)eval_node_aff(cf, c, t, nc, n, ctrl->ipa_lo[0], ctrl->ipa_hi[0], ctrl->fallback, &s, &passed);
+                k = passed ? pack_key(s, n + nc.base, 0) : 0;
+            } else {
+                k = eval_first_fit(cf, c, t, nc, n);
+            }
+        }
+        cnt += (uint32_t)__popcll(__ballot(k != 0));
+        if (__ballot(k > readlane64(top, 63)) == 0) continue;  // uniform: nothing enters the top 64
+        top = wave_merge_desc(top, wave_sort_desc(k));
+    }
+    if (lane == 0) s_cnt[wave] = cnt;
+    head_block_merge(s_top, top, wave, lane);
+    if (wave == 0) lists[(size_t)blockIdx.x * 64 + lane] = s_top[0][lane];
+    if (threadIdx.x == 0) {
+        uint32_t tot = 0;
+        for (int w = 0; w < kHeadWaves; ++w) tot += s_cnt[w];
+        bcnt[blockIdx.x] = tot;
+    }
+}
+
+__global__ __launch_bounds__(kBlock) void k_rank_head_merge(const uint64_t* lists, const uint32_t* bcnt, int nblk,
+                                                            uint64_t* out) {
+    __shared__ uint64_t s_top[kHeadWaves][64];
+    __shared__ uint32_t s_cnt[kHeadWaves];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    uint64_t top = 0;
+    for (int b = wave; b < nblk; b += kHeadWaves) top = wave_merge_desc(top, lists[(size_t)b * 64 + lane]);
+    uint32_t cnt = 0;
+    for (int b = threadIdx.x; b < nblk; b += kBlock) cnt += bcnt[b];
+    for (int o = 32; o > 0; o >>= 1) cnt += __shfl_xor(cnt, o, 64);
+    if (lane == 0) s_cnt[wave] = cnt;
+    head_block_merge(s_top, top, wave, lane);
+    if (wave == 0) out[lane] = s_top[0][lane];
+    if (threadIdx.x == 0) {
+        uint64_t tot = 0;
+        for (int w = 0; w < kHeadWaves; ++w) tot += s_cnt[w];
+        out[kTopK] = tot;
+    }
+}
+
+int rank_head_blocks(int n_nodes) {
+    const int need = n_nodes > 0 ? (n_nodes + kBlock - 1) / kBlock : 1;
+    const int cap = cu_count() < kHeadMaxBlocks ? cu_count() : kHeadMaxBlocks;
+    return need < cap ? need : cap;
+}
+// scratch, in 8-byte words: the result (kTopK keys + the count), the block lists, the block counts
+size_t rank_head_words() { return (size_t)(kTopK + 1) + (size_t)kHeadMaxBlocks * 64 + kHeadMaxBlocks / 2; }
+
+hipError_t launch_rank_head(const Conf& cf, const NodeCols& nc, const DevTables& t, const TaskClass& c,
+                            const PopCtrl* ctrl, int by_score, uint64_t* scratch, hipStream_t st) {
+    static_assert(kTopK == 64, "one key per lane");
+    uint64_t* out = scratch;
+    uint64_t* lists = scratch + kTopK + 1;
+    uint32_t* bcnt = reinterpret_cast<uint32_t*>(lists + (size_t)kHeadMaxBlocks * 64);
+    const int grid = rank_head_blocks(nc.n);
+    if (by_score && !c.aff && c.ipa_n == 0)
+        hipLaunchKernelGGL((k_rank_head<true>), dim3(grid), dim3(kBlock), 0, st, cf, nc, t, c, ctrl, by_score, lists,
+                           bcnt);
+    else
+        hipLaunchKernelGGL((k_rank_head<false>), dim3(grid), dim3(kBlock), 0, st, cf, nc, t, c, ctrl, by_score, lists,
+                           bcnt);
+    hipLaunchKernelGGL(k_rank_head_merge, dim3(1), dim3(kBlock), 0, st, (const uint64_t*)lists,
+                       (const uint32_t*)bcnt, grid, out);
+    return hipGetLastError();
+}
 
 hipError_t launch_node_op(const NodeCols& nc, const DevTables& t, int op, int n, int g, int cls, int64_t rc,
                           int64_t rm, int64_t rg, hipStream_t st) {

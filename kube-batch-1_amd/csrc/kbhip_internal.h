@@ -89,6 +89,16 @@ hipError_t launch_rank_sorted(const Conf& cf, const NodeCols& nc, const DevTable
                               const PopCtrl* ctrl, int by_score, int slo, int shi, uint64_t* keys, uint32_t* hist,
                               uint64_t* sorted, uint32_t* count, hipStream_t st);
 size_t rank_hist_words(int n_nodes);
+// The head of that order without a per-node array (kbhip_rank_nodes): a fused
+// predicate + score + top-kTopK sweep, then a one-block merge of the blocks'
+// lists.  Afterwards scratch[0 .. kTopK) = the best keys, descending (0 beyond
+// the passing count), scratch[kTopK] = the passing count; scratch holds
+// rank_head_words() 8-byte words.  ctrl task 0: the class, the fallback node
+// and the inter-pod prepass, as for launch_rank_nodes.
+int rank_head_blocks(int n_nodes);  // the sweep's grid
+size_t rank_head_words();
+hipError_t launch_rank_head(const Conf& cf, const NodeCols& nc, const DevTables& t, const TaskClass& c,
+                            const PopCtrl* ctrl, int by_score, uint64_t* scratch, hipStream_t st);
 // One session's ranking request in a batched launch (what-if sessions).
 struct RankDesc {
     Conf cf;

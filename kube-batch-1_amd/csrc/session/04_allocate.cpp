@@ -120,6 +120,56 @@ void rank_buffers(Session& S) {
     S.h_rank = (uint64_t*)MemPool::get().take(MemPool::kPinned, (size_t)(N + 1) * sizeof(uint64_t), &S.h_rank_cap);
 }
 
+// The device ranking of the task class cls on the session's stream: the keys
+// of the walk order (rank_nodes below; by_score: preempt, else reclaim) sorted
+// descending in b_rank_sorted, the passing count in b_rank_cnt[0] and the
+// nodes whose score left the class's range in b_rank_cnt[1].  Nothing is
+// copied back or waited for (the what-if batcher's shared launch aside).
+void rank_launch(Session& S, int cls, bool by_score) {
+    const int N = S.nc.n;
+    rank_buffers(S);
+    flush_tables(S);  // evictions / unevicts so far change pod-affinity predicates
+    ctrl_setup(S, 1, &cls, 0, 0, 0, 0, -1, 0);
+    HIPCHK(hipMemsetAsync(S.b_rank_cnt.p, 0, 2 * sizeof(uint32_t), S.stream));
+    auto sr = S.class_srange[cls];
+    if (by_score && S.classes[cls].ipa_n > 0) {  // inter-pod priority: normalisation prepass, wider range
+        HIPCHK(launch_ipa_minmax(S.nc, S.tab, S.d_ctrl, 0, S.stream));
+        exchange(S, &S.d_ctrl->ipa_lo[0], KBHIP_RED_MIN_I64);  // (shards: over every node)
+        exchange(S, &S.d_ctrl->ipa_hi[0], KBHIP_RED_MAX_I64);
+        const int64_t w = 10 * (int64_t)S.conf.w_pa * S.conf.score_mult;
+        sr.first += std::min<int64_t>(0, w);
+        sr.second += std::max<int64_t>(0, w);
+    }
+    const bool counting = !S.force_radix && sr.second - sr.first < 256 && sr.first >= INT32_MIN &&
+                          sr.second <= INT32_MAX;
+    if (counting && S.rank_group && S.world == 1) {  // one launch with the concurrent what-if sessions' rankings
+        StepBatcher::Req r;
+        r.kind = StepBatcher::kRank;
+        HIPCHK(fill_rank_desc(&r.rank, S.conf, S.nc, S.tab, S.classes[cls], S.d_ctrl, by_score ? 1 : 0, (int)sr.first,
+                              (int)sr.second, (uint64_t*)S.b_rank_keys.p, (uint32_t*)S.b_rank_tmp.p,
+                              (uint64_t*)S.b_rank_sorted.p, (uint32_t*)S.b_rank_cnt.p));
+        r.st = S.stream;
+        r.device = S.device;
+        HIPCHK(hipStreamSynchronize(S.stream));  // this request's control block and counters are in place
+        StepBatcher::get().submit(r);
+        HIPCHK(hipSetDevice(S.device));
+        HIPCHK(r.err);
+        S.stats.rank_requests++;
+        S.stats.rank_batch_sum += r.batch;
+    } else if (counting) {  // hand-written stable counting sort over the score
+        HIPCHK(launch_rank_sorted(S.conf, S.nc, S.tab, S.classes[cls], S.d_ctrl, by_score ? 1 : 0, (int)sr.first,
+                                  (int)sr.second,
+                                  (uint64_t*)S.b_rank_keys.p, (uint32_t*)S.b_rank_tmp.p,
+                                  (uint64_t*)S.b_rank_sorted.p, (uint32_t*)S.b_rank_cnt.p, S.stream));
+    } else {  // wide score ranges (large nodeorder weights): 8-bit LSD radix passes over the score
+        HIPCHK(launch_rank_nodes(S.conf, S.nc, S.tab, S.d_ctrl, by_score ? 1 : 0, (uint64_t*)S.b_rank_keys.p,
+                                 (uint32_t*)S.b_rank_cnt.p, S.stream));
+        HIPCHK(launch_rank_radix((const uint64_t*)S.b_rank_keys.p, N, (const uint32_t*)S.b_rank_cnt.p,
+                                 (uint32_t*)S.b_rank_tmp.p, (uint64_t*)S.b_rank_radix.p,
+                                 (uint64_t*)S.b_rank_sorted.p, S.stream));
+    }
+}
+
 struct Allocator {
     Session& S;
     explicit Allocator(Session& s) : S(s) {}
@@ -911,47 +961,7 @@ struct Allocator {
     }
     void rank_nodes_inner(int cls, bool by_score, vector<int>& out) {
         const int N = S.nc.n;
-        rank_buffers(S);
-        flush_tables(S);  // evictions / unevicts so far change pod-affinity predicates
-        ctrl_setup(S, 1, &cls, 0, 0, 0, 0, -1, 0);
-        HIPCHK(hipMemsetAsync(S.b_rank_cnt.p, 0, 2 * sizeof(uint32_t), S.stream));
-        auto sr = S.class_srange[cls];
-        if (by_score && S.classes[cls].ipa_n > 0) {  // inter-pod priority: normalisation prepass, wider range
-            HIPCHK(launch_ipa_minmax(S.nc, S.tab, S.d_ctrl, 0, S.stream));
-            exchange(S, &S.d_ctrl->ipa_lo[0], KBHIP_RED_MIN_I64);  // (shards: over every node)
-            exchange(S, &S.d_ctrl->ipa_hi[0], KBHIP_RED_MAX_I64);
-            const int64_t w = 10 * (int64_t)S.conf.w_pa * S.conf.score_mult;
-            sr.first += std::min<int64_t>(0, w);
-            sr.second += std::max<int64_t>(0, w);
-        }
-        const bool counting = !S.force_radix && sr.second - sr.first < 256 && sr.first >= INT32_MIN &&
-                              sr.second <= INT32_MAX;
-        if (counting && S.rank_group && S.world == 1) {  // one launch with the concurrent what-if sessions' rankings
-            StepBatcher::Req r;
-            r.kind = StepBatcher::kRank;
-            HIPCHK(fill_rank_desc(&r.rank, S.conf, S.nc, S.tab, S.classes[cls], S.d_ctrl, by_score ? 1 : 0, (int)sr.first,
-                                  (int)sr.second, (uint64_t*)S.b_rank_keys.p, (uint32_t*)S.b_rank_tmp.p,
-                                  (uint64_t*)S.b_rank_sorted.p, (uint32_t*)S.b_rank_cnt.p));
-            r.st = S.stream;
-            r.device = S.device;
-            HIPCHK(hipStreamSynchronize(S.stream));  // this request's control block and counters are in place
-            StepBatcher::get().submit(r);
-            HIPCHK(hipSetDevice(S.device));
-            HIPCHK(r.err);
-            S.stats.rank_requests++;
-            S.stats.rank_batch_sum += r.batch;
-        } else if (counting) {  // hand-written stable counting sort over the score
-            HIPCHK(launch_rank_sorted(S.conf, S.nc, S.tab, S.classes[cls], S.d_ctrl, by_score ? 1 : 0, (int)sr.first,
-                                      (int)sr.second,
-                                      (uint64_t*)S.b_rank_keys.p, (uint32_t*)S.b_rank_tmp.p,
-                                      (uint64_t*)S.b_rank_sorted.p, (uint32_t*)S.b_rank_cnt.p, S.stream));
-        } else {  // wide score ranges (large nodeorder weights): 8-bit LSD radix passes over the score
-            HIPCHK(launch_rank_nodes(S.conf, S.nc, S.tab, S.d_ctrl, by_score ? 1 : 0, (uint64_t*)S.b_rank_keys.p,
-                                     (uint32_t*)S.b_rank_cnt.p, S.stream));
-            HIPCHK(launch_rank_radix((const uint64_t*)S.b_rank_keys.p, N, (const uint32_t*)S.b_rank_cnt.p,
-                                     (uint32_t*)S.b_rank_tmp.p, (uint64_t*)S.b_rank_radix.p,
-                                     (uint64_t*)S.b_rank_sorted.p, S.stream));
-        }
+        rank_launch(S, cls, by_score);
         const int first = std::min(N, S.rank_first);
         HIPCHK(hipMemcpyAsync(S.h_rank, S.b_rank_cnt.p, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, S.stream));
         HIPCHK(hipMemcpyAsync(S.h_rank + 1, S.b_rank_sorted.p, first * sizeof(uint64_t), hipMemcpyDeviceToHost,

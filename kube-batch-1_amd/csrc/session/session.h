@@ -588,6 +588,9 @@ struct Session {
     DevBuf b_rank_keys, b_rank_sorted, b_rank_tmp, b_rank_cnt, b_rank_radix;
     DevBuf b_tab_idx;  // count-table deltas (flush_tables)
     DevBuf b_sweep_cnt;  // kbhip_sweep_scores' passing counts (8 counters, one 128-B line each)
+    DevBuf b_rank_head;  // kbhip_rank_nodes' head path: result, block lists, block counts (rank_head_words)
+    uint64_t* h_rank_head = nullptr;  // pinned: its kTopK keys, then the passing count
+    size_t h_rank_head_cap = 0;
     size_t rank_tmp_bytes = 0;
     uint64_t* h_rank = nullptr;  // pinned: [0] = count, then sorted keys
     size_t h_rank_cap = 0;
@@ -824,6 +827,8 @@ struct Session {
         eng_nw = 0;
         if (h_rank) MemPool::get().give(MemPool::kPinned, h_rank, h_rank_cap, device);
         h_rank = nullptr;
+        if (h_rank_head) MemPool::get().give(MemPool::kPinned, h_rank_head, h_rank_head_cap, device);
+        h_rank_head = nullptr;
         h_out = nullptr;
         if (cu_masked) {  // streams of option "cu_split" are this session's own
             for (int k = 1; k <= kMaxDep; ++k)
@@ -839,7 +844,7 @@ struct Session {
         for (DevBuf* b : {&b_labels, &b_taints, &b_ports, &b_classes, &b_terms, &b_reqs, &b_vals, &b_valint, &b_valok,
                           &b_masks, &b_ctrl, &b_walk, &b_dom, &b_aff_items, &b_aff_cnt, &b_aff_scalar, &b_cand2,
                           &b_arrive, &b_link, &b_dbg, &b_fit4, &b_rank_keys, &b_rank_sorted, &b_rank_tmp, &b_rank_cnt,
-                          &b_rank_radix,
+                          &b_rank_radix, &b_rank_head,
                           &b_shard_send, &b_shard_recv, &b_tab_idx, &b_sweep_cnt, &b_dd_max, &b_cmp_mask, &b_cmp_blk,
                           &b_cmp_node, &b_cmp_val})
             b->release();
@@ -1147,8 +1152,11 @@ void sweep_chunk(Session& S, int m, const int* cls, bool defer, bool per_task = 
 int take_slot(Session& S, uint32_t* epoch);
 void sweep_task(Session& S, int i, int cls, bool defer_visits = false);
 void rank_buffers(Session& S);
+void rank_launch(Session& S, int cls, bool by_score);
 void backfill_run(Session& S);
 int sweep_scores(Session& S, int pod, uint64_t* out_keys);
+int64_t rank_nodes_abi(Session& S, int pod, bool by_score, int64_t first, int32_t* out_node, int32_t* out_score,
+                       int64_t cap);
 int64_t walk_visits(Session& S, int32_t* out_node, uint32_t* out_count, int64_t cap);
 int64_t fit_deltas(Session& S, int pod, int32_t* out_node, int64_t* out_delta, int64_t cap);
 double time_sweeps(Session& S, const int32_t* ids, int n);

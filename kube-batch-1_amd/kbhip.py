@@ -31,7 +31,7 @@ EXPORTS = ("kbhip_device_count", "kbhip_session_open", "kbhip_session_open_file"
            "kbhip_first_fit", "kbhip_sweep_scores", "kbhip_shard_connect_host_gather",
            "kbhip_session_carry_events", "kbhip_shard_connect_mailbox", "kbhip_shard_mailbox_fits", "kbhip_place_job_submit",
            "kbhip_place_job_wait", "kbhip_place_job_cancel", "kbhip_time_sweeps", "kbhip_time_rank_multi",
-           "kbhip_session_carry_snapshot", "kbhip_walk_visits", "kbhip_fit_deltas")
+           "kbhip_session_carry_snapshot", "kbhip_walk_visits", "kbhip_fit_deltas", "kbhip_rank_nodes")
 
 RED_MAX_U64, RED_MIN_I64, RED_MAX_I64, RED_SUM_I64 = 0, 1, 2, 3
 ALLREDUCE_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint64), ctypes.c_int32,
@@ -63,7 +63,8 @@ class Stats(ctypes.Structure):
                 ("alloc_setup_s", ctypes.c_double), ("evict_setup_s", ctypes.c_double),
                 ("engine_pops", ctypes.c_int64), ("engine_launches", ctypes.c_int64),
                 ("engine_workers", ctypes.c_int64), ("engine_owners", ctypes.c_int64),
-                ("engine_not_resident", ctypes.c_int64)]
+                ("engine_not_resident", ctypes.c_int64), ("rank_heads", ctypes.c_int64),
+                ("rank_fulls", ctypes.c_int64)]
 
     def as_dict(self) -> dict:
         return {k: getattr(self, k) for k, _ in self._fields_}
@@ -128,6 +129,8 @@ def lib() -> ctypes.CDLL:
         L.kbhip_walk_visits.restype = i64
         L.kbhip_fit_deltas.argtypes = [vp, i32, vp, vp, i64]
         L.kbhip_fit_deltas.restype = i64
+        L.kbhip_rank_nodes.argtypes = [vp, i32, i32, i64, vp, vp, i64]
+        L.kbhip_rank_nodes.restype = i64
         _lib = L
     return _lib
 
@@ -218,6 +221,29 @@ class Session:
         out = np.zeros(max(n_nodes, 1), np.uint64)
         n = _check(lib().kbhip_sweep_scores(self._h, int(task_id), _p(out)))
         return n, out[:n_nodes].copy()
+
+    def rank_nodes(self, task_id: int, by_score: bool = True, first: int = 0,
+                   cap: Optional[int] = None) -> Tuple[int, np.ndarray, np.ndarray]:
+        """kbhip_rank_nodes: the ranked node walk of one pending task:
+        (total, nodes, scores) with entries [first, first + cap) of the walk.
+        by_score=True: preempt.go:270-287's util.SelectBestNode order of the
+        nodes passing PredicateFn with a NodeOrderFn score; False: reclaim's
+        walk, the passing nodes in ascending index (scores 0).  first + cap <=
+        64 is served by the top-64 kernel, anything else by the full device
+        sort.  cap=None: a size query, then every entry from `first`."""
+        bs = int(by_score)
+        if cap is None:
+            n = int(lib().kbhip_rank_nodes(self._h, int(task_id), bs, int(first), None, None, 0))
+            _check(n if n < 0 else 0)
+            cap = max(n - int(first), 0)
+            if cap == 0:
+                return n, np.zeros(0, np.int32), np.zeros(0, np.int32)
+        node = np.full(max(int(cap), 1), -1, np.int32)
+        score = np.zeros(max(int(cap), 1), np.int32)
+        n = int(lib().kbhip_rank_nodes(self._h, int(task_id), bs, int(first), _p(node), _p(score), int(cap)))
+        _check(n if n < 0 else 0)
+        k = max(min(n, int(first) + int(cap)) - int(first), 0)
+        return n, node[:k].copy(), score[:k].copy()
 
     def time_sweeps(self, task_ids) -> float:
         """kbhip_time_sweeps: device time per launch (us) of the standalone sweep,
