@@ -248,6 +248,46 @@ func (e *Engine) RankNodes(task int32, byScore bool, first, n int64) (total int6
 	return int64(t), nodes[:got], scores[:got], nil
 }
 
+// Op is one decision of a host-kept reclaim / preempt loop for ApplyOps.
+// Node is read for OpPipeline only (an eviction uses the pod's own node).
+type Op struct {
+	Kind uint8
+	Pod  int32
+	Node int32
+}
+
+// The operation kinds of ApplyOps (KBHIP_OP_*).
+const (
+	OpEvict      = uint8(C.KBHIP_OP_EVICT)      // Session.Evict / Statement.Evict
+	OpPipeline   = uint8(C.KBHIP_OP_PIPELINE)   // Session.Pipeline / Statement.Pipeline
+	OpUnpipeline = uint8(C.KBHIP_OP_UNPIPELINE) // Statement.unpipeline (a discarded statement)
+	OpUnevict    = uint8(C.KBHIP_OP_UNEVICT)    // Statement.unevict (the node keeps its Releasing copy)
+)
+
+// ApplyOps hands the engine what the host's own reclaim / preempt loop decided
+// since its last ranking (kbhip_apply_ops), in order: the session's host model
+// and the device node rows change exactly as under the engine's own actions,
+// so the next RankNodes sees them.  The batch is validated as a whole; on an
+// error nothing is changed.  Returns the device kernel launches issued (at
+// most 2 whatever len(ops) is).
+func (e *Engine) ApplyOps(ops []Op) (launches int64, err error) {
+	if len(ops) == 0 { // &kind[0] of an empty slice panics
+		return 0, nil
+	}
+	kind := make([]uint8, len(ops))
+	pod := make([]int32, len(ops))
+	node := make([]int32, len(ops))
+	for i, o := range ops {
+		kind[i], pod[i], node[i] = o.Kind, o.Pod, o.Node
+	}
+	var l C.int64_t
+	if n := C.kbhip_apply_ops(e.s, (*C.uint8_t)(unsafe.Pointer(&kind[0])), (*C.int32_t)(unsafe.Pointer(&pod[0])),
+		(*C.int32_t)(unsafe.Pointer(&node[0])), C.int64_t(len(ops)), &l); n < 0 {
+		return 0, lastErr("apply_ops", C.int(n))
+	}
+	return int64(l), nil
+}
+
 // GangUnschedulable is the gang plugin's OnSessionClose text after Allocate
 // (gang.go:166-187): "<job uid>\t<message>\n" per job that is not ready.
 func (e *Engine) GangUnschedulable() (string, error) {

@@ -246,6 +246,59 @@ int kbhip_sweep_scores(kb_session* s, int32_t task_id, uint64_t* out_keys);
 int64_t kbhip_rank_nodes(kb_session* s, int32_t task_id, int32_t by_score, int64_t first, int32_t* out_node,
                          int32_t* out_score, int64_t cap);
 
+/* kbhip_apply_ops <- the evictions and pipelines a host that keeps reclaim's /
+ * preempt's own loop decided since its last ranking: n operations, applied in
+ * the given order to the session's host model and to the device exactly as
+ * the engine's own reclaim / preempt actions apply theirs, so the next
+ * kbhip_rank_nodes / kbhip_sweep_scores / kbhip_first_fit, every later action
+ * and every carry-over run on the state the host's loop has reached.
+ *   KBHIP_OP_EVICT pod       Session.Evict / Statement.Evict (session.go:331-356,
+ *     statement.go:35-67).  pod is Running and so is its node's copy (what the
+ *     reclaimee / preemptee filters admit).  Its status becomes Releasing, its
+ *     node's Releasing grows by its Resreq, it stops being a pod-affinity
+ *     predicate target, the drf / proportion deallocate handlers run.  node[i]
+ *     is ignored: the pod's own node is used.
+ *   KBHIP_OP_PIPELINE pod, node   Session.Pipeline / Statement.Pipeline
+ *     (session.go:199-235, statement.go:96-136).  pod is a Pending task with a
+ *     task class, node is in range.  Status Pipelined on node, the node row is
+ *     committed with kind Pipelined (pod count, non-zero requests, host ports,
+ *     Releasing), the inter-pod fallback node follows, the allocate handlers
+ *     run.  No predicate or fit check: the host decided, as ssn.Pipeline does.
+ *   KBHIP_OP_UNPIPELINE pod  Statement.unpipeline (statement.go:141-172): the
+ *     reverse, for a pod an earlier KBHIP_OP_PIPELINE pipelined.
+ *   KBHIP_OP_UNEVICT pod     Statement.unevict (statement.go:81-105), for a pod
+ *     an earlier KBHIP_OP_EVICT evicted: Running in the session and a
+ *     predicate target again, while its node keeps the Releasing copy (the
+ *     failing node.AddTask of the reference): the node's Releasing stays and
+ *     the pod is no victim candidate any more.
+ * A carry-over ends "earlier": operations do not reach across it.
+ * The whole batch is validated first, against the statuses as the batch
+ * itself changes them; on a validation error (KBHIP_EINVAL,
+ * KBHIP_EUNSUPPORTED) nothing is changed.  A device or allocation failure
+ * after validation (KBHIP_EDEVICE) can leave a partly applied batch, as a
+ * failed action does: close the session and open a new one.  KBHIP_EINVAL: a
+ * null session, a null op, pod or node array with n > 0, n < 0 or above
+ * 2^31 - 1, an unknown operation, a pod or a KBHIP_OP_PIPELINE node out of range,
+ * an operation that does not fit the pod's status, an encode-only session,
+ * submitted pops outstanding; KBHIP_EUNSUPPORTED on node-sharded sessions (as
+ * the other per-task calls).  Returns n (0 for an empty batch: nothing done).
+ * On the device the batch's node operations are grouped by node on the host
+ * and applied by one kernel, a lane per distinct node walking its operations
+ * in order; the predicate-target changes of evictions / unevicts follow in
+ * one count-table launch, done before the call returns.  *out_launches
+ * (optional) = the device kernel launches the call issued: at most 2 whatever
+ * n is.  No output record is produced (the host has its decisions), the
+ * counters of kbhip_walk_visits are untouched, and a task kbhip_fit_deltas
+ * would have answered for is no longer answerable, as after any call that
+ * places.  A task pipelined here is not Pending: kbhip_rank_nodes refuses it
+ * until a KBHIP_OP_UNPIPELINE. */
+#define KBHIP_OP_EVICT 1
+#define KBHIP_OP_PIPELINE 2
+#define KBHIP_OP_UNPIPELINE 3
+#define KBHIP_OP_UNEVICT 4
+int64_t kbhip_apply_ops(kb_session* s, const uint8_t* op, const int32_t* pod, const int32_t* node, int64_t n,
+                        int64_t* out_launches);
+
 /* Measurement hook (bench.py's sweep roofline): kbhip_sweep_scores' sweep
  * kernel for each given task, launched back to back on the session stream
  * with no copies in between; *out_mean_us = device time per launch (one

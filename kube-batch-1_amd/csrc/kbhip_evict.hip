@@ -258,6 +258,88 @@ __global__ __launch_bounds__(64) void k_node_op(NodeCols nc, DevTables t, int op
     }
 }
 
+// A batch of those node-row updates in one launch (kbhip_apply_ops: the
+// evictions and pipelines a host-driven reclaim / preempt loop decided).  The
+// host groups the batch stably by node (ApplyOps: CSR over the distinct
+// nodes); lane i owns node seg_node[i] and walks its operations
+// [seg_off[i], seg_off[i + 1]) in batch order, so no two lanes touch one row:
+// the row columns take plain loads and stores and the result does not depend
+// on scheduling.  The walk changes nothing in memory but the host-port words:
+// what the operations do to the row's integer columns — an eviction's
+// Releasing += Resreq, and commit_node(…, 2) / uncommit_node(…, 2) of a
+// pipeline / unpipeline: Backfilled ± request for a backfill class, Releasing
+// ∓ request, pod count ± 1, non-zero requests ± — is summed in registers with
+// the operation's sign and added to the row once after the walk (integer adds
+// commute: the row is the one the operations leave one launch each, bit for
+// bit).  A first version ran commit_node / uncommit_node on the row in memory
+// inside the walk; segments of a few dozen pipelines and unpipelines of
+// different classes then lost updates on the device, while short segments and
+// segments of one kind came out right from the same host grouping
+// (tests/test_gpu_apply_ops.py test_after_an_engine_action holds the case).
+// Why that single-lane chain of read-modify-writes through memory went wrong
+// was not established; this form has no such chain.  The
+// port words are or-ed / and-not-ed in order, by a select, not a branch.  The
+// count-table half of a
+// pipeline / unpipeline of a pod-affinity class (commit_aff, kind 2: the
+// session-placed counters) can meet another node's lane on one entry: device-
+// scope atomic adds, in commit_task's branch-free form — integer adds, so the
+// tables do not depend on the order either.
+__device__ __forceinline__ void aff_add(const TaskClass& c, const DevTables& t, const NodeCols& nc, int g, int kind,
+                                        int sign) {
+    for (int i = 0; i < c.upd_n; ++i) {
+        const int32_t* u = t.aff_items + c.upd_off + 3 * i;
+        const bool to_cnt = u[0] == 0;
+        const int d = to_cnt ? dom_g(nc, u[1], g) : 0;
+        const bool apply = (u[0] == 2 || kind == 1) && d >= 0;
+        int32_t* tab = to_cnt ? t.aff_cnt : t.aff_scalar;
+        __hip_atomic_fetch_add(tab + u[2] + (d >= 0 ? d : 0), apply ? sign : 0, __ATOMIC_RELAXED,
+                               __HIP_MEMORY_SCOPE_AGENT);
+    }
+}
+__global__ __launch_bounds__(kBlock) void k_apply_ops(NodeCols nc, DevTables t, ApplyOps a) {
+    const int i = blockIdx.x * kBlock + threadIdx.x;
+    if (i >= a.n_seg) return;
+    const int n = a.seg_node[i];
+    if (n < 0 || n >= nc.n) return;  // (the host validated the batch)
+    int64_t rc = 0, rm = 0, rg = 0;  // Releasing
+    int64_t bc = 0, bm = 0, bg = 0;  // Backfilled
+    int64_t zc = 0, zm = 0;          // non-zero requests
+    int32_t dp = 0;                  // pod count
+    const int j1 = a.seg_off[i + 1];
+    for (int j = a.seg_off[i]; j < j1; ++j) {
+        const int32_t kc = a.kind_cls[j];
+        const int op = kc & 3;
+        if (op == 0) {
+            rc += a.req[3 * (size_t)j]; rm += a.req[3 * (size_t)j + 1]; rg += a.req[3 * (size_t)j + 2];
+            continue;
+        }
+        const TaskClass& c = t.classes[kc >> 2];
+        const int sg = op == 1 ? 1 : -1;          // pipeline / unpipeline
+        const int64_t s = sg, b = c.backfill ? s : 0;
+        bc += b * c.req_cpu; bm += b * c.req_mem; bg += b * c.req_gpu;
+        rc -= s * c.req_cpu; rm -= s * c.req_mem; rg -= s * c.req_gpu;
+        dp += sg;
+        zc += s * c.nz_cpu;
+        zm += s * c.nz_mem;
+        if (c.has_ports)
+            for (int w = 0; w < 4; ++w) if (w < port_win(c, nc)) {
+                const size_t at = port_at(c, nc, w, n);
+                const uint64_t v = nc.ports[at], m = t.masks[c.pown_off + w];
+                nc.ports[at] = sg > 0 ? (v | m) : (v & ~m);
+            }
+        if (c.aff) aff_add(c, t, nc, n + nc.base, 2, sg);
+    }
+    nc.rel_cpu[n] += rc; nc.rel_mem[n] += rm; nc.rel_gpu[n] += rg;
+    if (bc | bm | bg) { nc.bf_cpu[n] += bc; nc.bf_mem[n] += bm; nc.bf_gpu[n] += bg; }
+    if (dp | zc | zm) { nc.pods[n] += dp; nc.nzc[n] += zc; nc.nzm[n] += zm; }
+}
+
+hipError_t launch_apply_ops(const NodeCols& nc, const DevTables& t, const ApplyOps& a, hipStream_t st) {
+    if (a.n_seg <= 0) return hipSuccess;
+    hipLaunchKernelGGL(k_apply_ops, dim3((a.n_seg + kBlock - 1) / kBlock), dim3(kBlock), 0, st, nc, t, a);
+    return hipGetLastError();
+}
+
 // Count-table changes queued on the host (evictions / unevicts of predicate
 // targets, session/03_pop.cpp flush_tables): idx >= 0 -> aff_cnt[idx],
 // idx < 0 -> aff_scalar[-1 - idx]; the indices are distinct.

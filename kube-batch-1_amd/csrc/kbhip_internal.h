@@ -130,6 +130,19 @@ hipError_t launch_row_patch(const RowPatch* e, int n, hipStream_t st);
 hipError_t launch_node_op(const NodeCols& nc, const DevTables& t, int op, int n, int g, int cls, int64_t rc,
                           int64_t rm, int64_t rg, hipStream_t st);
 
+// A batch of those updates grouped stably by node (kbhip_apply_ops; device pointers): segment i holds the
+// operations [seg_off[i], seg_off[i + 1]) of local row seg_node[i] in batch order (the rows are distinct);
+// operation j is kind_cls[j] & 3 (the op above) on class kind_cls[j] >> 2, an eviction's Resreq in req[3 j ..].
+struct ApplyOps {
+    const int32_t* seg_node;
+    const int32_t* seg_off;  // n_seg + 1 entries
+    const int32_t* kind_cls;
+    const int64_t* req;
+    int n_seg;
+};
+// One lane per segment, as many blocks as the segments need (one launch whatever the batch holds).
+hipError_t launch_apply_ops(const NodeCols& nc, const DevTables& t, const ApplyOps& a, hipStream_t st);
+
 // Selection-key format of a batched launch: 32-bit keys when the class's
 // score range and the node count fit (kbhip_kernels.hip, PopArgs).
 struct KeyFormat {

@@ -855,19 +855,20 @@ void queue_target(Session& S, int pi, int sign) {
         }
     }
 }
-void flush_tables(Session& S) {
-    if (S.tab_delta.empty()) return;
+int flush_tables(Session& S) {
+    if (S.tab_delta.empty()) return 0;
     vector<int32_t> idx, val;
     for (auto& kv : S.tab_delta)
         if (kv.second) { idx.push_back((int32_t)kv.first); val.push_back(kv.second); }
     S.tab_delta.clear();
-    if (idx.empty()) return;
+    if (idx.empty()) return 0;
     const int n = (int)idx.size();
     int32_t* di = S.b_tab_idx.alloc<int32_t>(2 * (size_t)n);
     idx.insert(idx.end(), val.begin(), val.end());
     HIPCHK(hipMemcpyAsync(di, idx.data(), idx.size() * sizeof(int32_t), hipMemcpyHostToDevice, S.stream));
     HIPCHK(launch_tab_add(S.tab, di, di + n, n, S.stream));
     HIPCHK(hipStreamSynchronize(S.stream));  // the pageable source must outlive the copy
+    return 1;
 }
 
 // Host mirror of the device commits of consumed tasks (NodeInfo.Used, the

@@ -1009,8 +1009,13 @@ struct Allocator {
             out[i] = key_idx(recv[at[best]++]);
         }
     }
+    // kbhip_apply_ops (apply_ops_model below): the four operations run on the host model as in the
+    // actions, their node-row halves collected here in order instead of launched or summed (the caller
+    // applies them in one launch, launch_apply_ops)
+    vector<NodeOp>* ops_out = nullptr;
     void dev_op(int op, int pi) {  // the row on the owning shard, the count tables on every shard
         const HPod& p = S.pods[pi];
+        if (ops_out) { ops_out->push_back(NodeOp{op, p.node, p.cls, R3{}}); return; }
         HIPCHK(launch_node_op(S.nc, S.tab, op, local_node(p.node), p.node, p.cls, p.req.c, p.req.m, p.req.g,
                               S.stream));
     }
@@ -1021,6 +1026,11 @@ struct Allocator {
         // node.UpdateTask: Releasing += Resreq.  No node ranking reads Releasing, so
         // evictions are summed per node and applied in one launch (flush_evictions)
         const HPod& p = S.pods[v];
+        if (ops_out) {
+            ops_out->push_back(NodeOp{0, p.node, 0, p.req});
+            on_deallocate(v);
+            return;
+        }
         if (S.rel_delta.empty()) { S.rel_delta.assign(S.n_total, R3{}); S.rel_flag.assign(S.n_total, 0); }
         if (!S.rel_flag[p.node]) { S.rel_flag[p.node] = 1; S.rel_touched.push_back(p.node); }
         R3& d = S.rel_delta[p.node];
@@ -1066,8 +1076,13 @@ struct Allocator {
         HPod& p = S.pods[t];
         set_status(t, Pipelined);
         p.node = n;
-        auto& nt = S.node_tasks[n];
-        nt.insert(std::lower_bound(nt.begin(), nt.end(), t), t);
+        // NodeInfo.Tasks exists while an eviction action runs (build_node_tasks at its start; every such
+        // action rebuilds it); between actions (kbhip_apply_ops) a list left by an earlier action takes
+        // the operations' inserts and erases and nothing is built: the next eviction action reads the pods
+        if (n < (int)S.node_tasks.size()) {
+            auto& nt = S.node_tasks[n];
+            nt.insert(std::lower_bound(nt.begin(), nt.end(), t), t);
+        }
         dev_op(1, t);
         S.used[n].c += p.req.c; S.used[n].m += p.req.m; S.used[n].g += p.req.g;
         sess_placed(S, n, +1);
@@ -1077,8 +1092,10 @@ struct Allocator {
     void unpipeline(int t) {  // statement.go:141-172 (task.NodeName stays set)
         HPod& p = S.pods[t];
         set_status(t, Pending);
-        auto& nt = S.node_tasks[p.node];
-        nt.erase(std::lower_bound(nt.begin(), nt.end(), t));
+        if (p.node < (int)S.node_tasks.size()) {
+            auto& nt = S.node_tasks[p.node];
+            nt.erase(std::lower_bound(nt.begin(), nt.end(), t));  // (a list that exists holds every Pipelined task)
+        }
         dev_op(2, t);
         S.used[p.node].c -= p.req.c; S.used[p.node].m -= p.req.m; S.used[p.node].g -= p.req.g;
         sess_placed(S, p.node, -1);
@@ -1488,6 +1505,27 @@ void evict_run(Session& S, bool preempt) {
     Allocator a(S);
     if (preempt) a.preempt_action();
     else a.reclaim_action();
+}
+// kbhip_apply_ops: a validated batch (10_ops.cpp) through the operations above.  The action object is
+// new: its per-action caches (run_copy, readyTaskNum) are empty, which set_status and unevict leave
+// alone, and the next eviction action builds its own from the pods (reset_ready_cache,
+// build_node_tasks, compile_victims); Session::pod_queue holds no status.  drf / proportion open
+// first (on the statuses before the batch, as OnSessionOpen sees them), so the event handlers change
+// what a later action reads.
+void apply_ops_model(Session& S, const uint8_t* op, const int32_t* pod, const int32_t* node, int64_t n,
+                     vector<NodeOp>& out) {
+    S.fit_task = -1;
+    Allocator a(S);
+    a.open_plugins();
+    a.ops_out = &out;
+    for (int64_t i = 0; i < n; ++i) {
+        switch (op[i]) {
+            case KBHIP_OP_EVICT: a.evict_in_session(pod[i]); break;
+            case KBHIP_OP_PIPELINE: a.pipeline(pod[i], node[i]); break;
+            case KBHIP_OP_UNPIPELINE: a.unpipeline(pod[i]); break;
+            default: a.unevict(pod[i]); break;
+        }
+    }
 }
 
 // ---------------------------------------------------------------------------

@@ -607,6 +607,21 @@ struct Session {
     vector<int32_t> rel_touched;     // nodes with a rel_delta entry, in first-touch order
     vector<uint8_t> rel_flag;        // node is in rel_touched
     DevBuf b_rel_nodes, b_rel_d;
+    // kbhip_apply_ops (10_ops.cpp): a batch's node operations grouped by node, written to pinned staging
+    // and copied to b_ops without a wait — ev_ops marks the copy's end, waited for before the staging is
+    // written again.  ops_seg[node] = the node's segment in the batch being grouped (-1 between calls).
+    // op_mark[pod]: bit 0 evicted, bit 1 pipelined by an operation of this session model (op_mark_gen ==
+    // model_gen; a carry-over ends both); ops_sim[pod] = the pod's status as the batch under validation
+    // left it (-1 between calls).
+    DevBuf b_ops;
+    size_t b_ops_bytes = 0;
+    uint8_t* h_ops = nullptr;  // pinned
+    size_t h_ops_cap = 0;
+    hipEvent_t ev_ops = nullptr;
+    vector<int32_t> ops_seg;
+    vector<int32_t> ops_sim;
+    vector<uint8_t> op_mark;
+    uint64_t op_mark_gen = ~0ull;
     int32_t fallback = -1;  // lowest node index holding a session-placed pod (nodeorder.go:78-93)
     vector<int32_t> sess_cnt;  // per node: session-placed pods on it (fallback after an unpipeline)
     std::unique_ptr<AffinityModel> aff;       // pod (anti-)affinity model (kept for evictions / carry)
@@ -829,6 +844,10 @@ struct Session {
         h_rank = nullptr;
         if (h_rank_head) MemPool::get().give(MemPool::kPinned, h_rank_head, h_rank_head_cap, device);
         h_rank_head = nullptr;
+        if (h_ops) MemPool::get().give(MemPool::kPinned, h_ops, h_ops_cap, device);
+        h_ops = nullptr;
+        if (ev_ops) { (void)hipEventDestroy(ev_ops); ev_ops = nullptr; }
+        b_ops.release();
         h_out = nullptr;
         if (cu_masked) {  // streams of option "cu_split" are this session's own
             for (int k = 1; k <= kMaxDep; ++k)
@@ -1134,7 +1153,7 @@ void ev_harvest_all(Session& S);
 void exchange(Session& S, void* dev, int op, int n = 1);
 void gather_host(Session& S, const void* send, void* recv, size_t bytes);
 void fit_allreduce(Session& S, int32_t* fit4);
-void flush_tables(Session& S);
+int flush_tables(Session& S);  // the kernel launches it issued (0 or 1)
 BatchLaunch launch_batched(Session& S, int cls, int m, int gang_mode, int min_avail, int ready_count);
 void ov_quiesce(Session& S);
 void ov_fence(Session& S);
@@ -1172,6 +1191,19 @@ void reopen_in_place(kb_session* ks, const kbs::Snapshot& s);
 void allocate_run(Session& S);
 void evict_run(Session& S, bool preempt);
 void first_fit(Session& S, const int32_t* ids, int n, int32_t* out_node);
+// kbhip_apply_ops: the node-row half of one operation, as the host model's evict_in_session / pipeline /
+// unpipeline hand it over (kind: launch_node_op's op; node: global index; cls: the task class, 0 for an
+// eviction; req: the evicted pod's Resreq)
+struct NodeOp {
+    int32_t kind, node, cls;
+    R3 req;
+};
+// The host-model half of a validated batch (04_allocate.cpp: the eviction actions' own operations, in
+// order); out = the batch's node operations in order, none of them launched.
+void apply_ops_model(Session& S, const uint8_t* op, const int32_t* pod, const int32_t* node, int64_t n,
+                     vector<NodeOp>& out);
+int64_t apply_ops(Session& S, const uint8_t* op, const int32_t* pod, const int32_t* node, int64_t n,
+                  int64_t* out_launches);
 
 }  // namespace kbhip
 

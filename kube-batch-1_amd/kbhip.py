@@ -20,6 +20,7 @@ LIB_PATH = os.environ.get("KBHIP_LIB") or os.path.join(HERE, "_build", "libkbhip
 ALLOCATED, PIPELINED, EVICTED = 1, 2, 3
 EV_DELETE, EV_SUCCEEDED, EV_FAILED = 1, 2, 3  # kbhip_session_carry_events
 STOP_ALL, STOP_UNASSIGNED, STOP_READY = 0, 1, 2
+OP_EVICT, OP_PIPELINE, OP_UNPIPELINE, OP_UNEVICT = 1, 2, 3, 4  # kbhip_apply_ops
 
 # int kbhip_* entry points declared by include/kbhip.h
 EXPORTS = ("kbhip_device_count", "kbhip_session_open", "kbhip_session_open_file", "kbhip_place_job",
@@ -31,7 +32,8 @@ EXPORTS = ("kbhip_device_count", "kbhip_session_open", "kbhip_session_open_file"
            "kbhip_first_fit", "kbhip_sweep_scores", "kbhip_shard_connect_host_gather",
            "kbhip_session_carry_events", "kbhip_shard_connect_mailbox", "kbhip_shard_mailbox_fits", "kbhip_place_job_submit",
            "kbhip_place_job_wait", "kbhip_place_job_cancel", "kbhip_time_sweeps", "kbhip_time_rank_multi",
-           "kbhip_session_carry_snapshot", "kbhip_walk_visits", "kbhip_fit_deltas", "kbhip_rank_nodes")
+           "kbhip_session_carry_snapshot", "kbhip_walk_visits", "kbhip_fit_deltas", "kbhip_rank_nodes",
+           "kbhip_apply_ops")
 
 RED_MAX_U64, RED_MIN_I64, RED_MAX_I64, RED_SUM_I64 = 0, 1, 2, 3
 ALLREDUCE_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint64), ctypes.c_int32,
@@ -131,6 +133,8 @@ def lib() -> ctypes.CDLL:
         L.kbhip_fit_deltas.restype = i64
         L.kbhip_rank_nodes.argtypes = [vp, i32, i32, i64, vp, vp, i64]
         L.kbhip_rank_nodes.restype = i64
+        L.kbhip_apply_ops.argtypes = [vp, vp, vp, vp, i64, vp]
+        L.kbhip_apply_ops.restype = i64
         _lib = L
     return _lib
 
@@ -244,6 +248,24 @@ class Session:
         _check(n if n < 0 else 0)
         k = max(min(n, int(first) + int(cap)) - int(first), 0)
         return n, node[:k].copy(), score[:k].copy()
+
+    def apply_ops(self, ops, pods, nodes=None) -> int:
+        """kbhip_apply_ops: the evictions and pipelines a host-driven reclaim /
+        preempt loop decided (OP_EVICT / OP_PIPELINE / OP_UNPIPELINE /
+        OP_UNEVICT per pod, in order; nodes: the node of each OP_PIPELINE,
+        ignored otherwise) applied to the host model and the device as the
+        engine's own actions apply theirs.  Returns the device kernel launches
+        the call issued."""
+        o = np.ascontiguousarray(ops, dtype=np.uint8)
+        p = np.ascontiguousarray(pods, dtype=np.int32)
+        nd = np.zeros(p.size, np.int32) if nodes is None else np.ascontiguousarray(nodes, dtype=np.int32)
+        if not (o.ndim == p.ndim == nd.ndim == 1 and o.size == p.size == nd.size):
+            raise ValueError("ops, pods and nodes differ in length")
+        launches = np.zeros(1, np.int64)
+        n = int(lib().kbhip_apply_ops(self._h, _p(o) if o.size else None, _p(p) if p.size else None,
+                                      _p(nd) if nd.size else None, int(o.size), _p(launches)))
+        _check(n if n < 0 else 0)
+        return int(launches[0])
 
     def time_sweeps(self, task_ids) -> float:
         """kbhip_time_sweeps: device time per launch (us) of the standalone sweep,
