@@ -1156,7 +1156,7 @@ hipError_t launch_sweep_multi(const SweepReq* reqs, int n, int k, hipStream_t st
     return hipGetLastError();
 }
 
-// Retraction of a batched pop whose prediction failed (Allocator::speculate):
+// Retraction of a batched pop whose prediction failed (Speculation::speculate):
 // the inverse node updates of its placements, in one lane (a node may appear
 // several times).
 struct UndoArgs {

@@ -1005,7 +1005,7 @@ int place_job(Session& S, const int32_t* ids, int n, int gang_mode, int min_avai
 
 // ---------------------------------------------------------------------------
 // asynchronous per-pop ABI (kbhip_place_job_submit / _wait / _cancel): the
-// pipelining of kbhip_allocate's speculation (Allocator::speculate), offered
+// pipelining of kbhip_allocate's speculation (Speculation::speculate), offered
 // to a host that keeps allocate.go's loop itself.  A submitted pop runs on the
 // device state its predecessors leave; launched tickets form a prefix of the
 // queue (a deferred one, run at its wait, holds back the ones behind it).

@@ -1,5 +1,5 @@
 // kbhip session, part 10: host-decided evictions and pipelines (kbhip_apply_ops)
-#include "session.h"
+#include "framework.h"
 
 namespace kbhip {
 
@@ -71,6 +71,26 @@ void commit_marks(Session& S, const uint8_t* op, const int32_t* pod, int64_t n) 
             case KBHIP_OP_PIPELINE: m |= kMarkPipelined; break;
             case KBHIP_OP_UNPIPELINE: m &= (uint8_t)~kMarkPipelined; break;
             default: m &= (uint8_t)~kMarkEvicted; break;
+        }
+    }
+}
+
+// The host-model half of a validated batch: the eviction actions' own statement operations
+// (framework.h), in order; out = the batch's node operations in order, none of them launched.
+// drf / proportion open first (on the statuses before the batch, as OnSessionOpen sees them), so
+// the event handlers change what a later action reads.
+void apply_ops_model(Session& S, const uint8_t* op, const int32_t* pod, const int32_t* node, int64_t n,
+                     vector<NodeOp>& out) {
+    S.fit_task = -1;
+    Framework F(S);
+    F.open_plugins();
+    F.ops_out = &out;
+    for (int64_t i = 0; i < n; ++i) {
+        switch (op[i]) {
+            case KBHIP_OP_EVICT: F.evict_in_session(pod[i]); break;
+            case KBHIP_OP_PIPELINE: F.pipeline(pod[i], node[i]); break;
+            case KBHIP_OP_UNPIPELINE: F.unpipeline(pod[i]); break;
+            default: F.unevict(pod[i]); break;
         }
     }
 }

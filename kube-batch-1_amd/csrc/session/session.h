@@ -5,11 +5,14 @@
 //
 // The parts: 02_open (session open: KBS1 decode, dictionary encoding, task
 // classes, upload of the node SoA to HBM), 03_pop (the per-pop device driver:
-// batched pops, the persistent engine, tickets), 04_allocate (a C++ mirror of
-// the Go framework's ordering plugins running the allocate / reclaim /
-// preempt actions), 05_actions (backfill, the standalone sweeps, the actions'
-// C-ABI entry points), 06_carry (session carry-over), 07_abi (the remaining
-// C-ABI entry points).
+// batched pops, the persistent engine, tickets), 04_allocate (the allocate
+// action and its speculation, first_fit), 05_actions (backfill, the standalone
+// sweeps, the actions' C-ABI entry points), 06_carry (session carry-over),
+// 07_abi (the remaining C-ABI entry points), 08_walk (the walk read-outs),
+// 09_rank (kbhip_rank_nodes), 10_ops (kbhip_apply_ops), 11_evict (the reclaim /
+// preempt actions and the device ranking of a task's nodes).  framework.h, which
+// the parts running actions include, is the C++ mirror of the Go framework they
+// share: the heaps, the ordering plugins, the status index, the statements.
 //
 // Reference map (pkg/scheduler unless noted):
 //   session open      cache/cache.go:515-583 (Snapshot), framework/session.go:66-122,
@@ -520,7 +523,7 @@ inline SpareVec<string>& spare_uids() {
 // ---------------------------------------------------------------------------
 // batched pop launches: one k_pop_batch per job-pop chunk of one class.  Two
 // result slots, so that the predicted next pop can be queued on the stream
-// behind a running one (Allocator::speculate) and its results told apart.
+// behind a running one (Speculation::speculate, 04_allocate.cpp) and its results told apart.
 // ---------------------------------------------------------------------------
 struct BatchLaunch {
     int slot = 0;
@@ -579,7 +582,7 @@ struct Session {
     // fitting node lies below the list of walked nodes, or there is none) sends the class's
     // next pops to the general path directly (same records either way)
     vector<uint8_t> bf_backoff;
-    // reclaim / preempt: each pod's job queue and MinAvailable (Allocator::compile_victims), valid
+    // reclaim / preempt: each pod's job queue and MinAvailable (EvictAction::compile_victims, 11_evict.cpp), valid
     // while pod_queue_gen == model_gen (every carry-over bumps model_gen)
     vector<int32_t> pod_queue, pod_min;
     uint64_t model_gen = 0, pod_queue_gen = ~0ull;
@@ -1191,17 +1194,13 @@ void reopen_in_place(kb_session* ks, const kbs::Snapshot& s);
 void allocate_run(Session& S);
 void evict_run(Session& S, bool preempt);
 void first_fit(Session& S, const int32_t* ids, int n, int32_t* out_node);
-// kbhip_apply_ops: the node-row half of one operation, as the host model's evict_in_session / pipeline /
+// kbhip_apply_ops: the node-row half of one operation, as the Framework's evict_in_session / pipeline /
 // unpipeline hand it over (kind: launch_node_op's op; node: global index; cls: the task class, 0 for an
 // eviction; req: the evicted pod's Resreq)
 struct NodeOp {
     int32_t kind, node, cls;
     R3 req;
 };
-// The host-model half of a validated batch (04_allocate.cpp: the eviction actions' own operations, in
-// order); out = the batch's node operations in order, none of them launched.
-void apply_ops_model(Session& S, const uint8_t* op, const int32_t* pod, const int32_t* node, int64_t n,
-                     vector<NodeOp>& out);
 int64_t apply_ops(Session& S, const uint8_t* op, const int32_t* pod, const int32_t* node, int64_t n,
                   int64_t* out_launches);
 
