@@ -248,6 +248,60 @@ func (e *Engine) RankNodes(task int32, byScore bool, first, n int64) (total int6
 	return int64(t), nodes[:got], scores[:got], nil
 }
 
+// The victim kinds of RankVictimNodes (KBHIP_VICTIMS_*): whose Running tasks
+// the caller's loop filters for.
+const (
+	VictimsOtherQueues    int32 = 1 // reclaim.go: jobs of other queues
+	VictimsQueueOtherJobs int32 = 2 // preempt.go:104-127: the task's queue, other jobs
+	VictimsSameJob        int32 = 3 // preempt.go:151-181: the task's own job
+)
+
+// VictimWalkInfo says how a RankVictimNodes call was served.
+type VictimWalkInfo struct {
+	Head     bool  // by the top-64 kernel
+	Rebuilt  bool  // the call (re)built the candidate table
+	Launches int64 // kernel launches issued
+}
+
+// RankVictimNodes is RankNodes without the nodes that can yield no victim set
+// for the task (kbhip_rank_victim_nodes): nodes with no candidate of the
+// given kind, or whose candidates' Resreq sum is strictly below the task's
+// InitResreq in all three resources — the nodes validateVictims rejects
+// whatever the plugins answer.  cands[i] is the candidate count of nodes[i].
+// The host loop over this walk decides what the loop over RankNodes' walk
+// decides, in the same order.  ApplyOps keeps the device's candidate table
+// current; any other call that changes pod statuses makes the next call here
+// rebuild it.
+func (e *Engine) RankVictimNodes(task int32, byScore bool, victims int32, first, n int64) (total int64, nodes, scores, cands []int32, info VictimWalkInfo, err error) {
+	if n < 0 || first < 0 {
+		return 0, nil, nil, nil, info, fmt.Errorf("kbhip rank_victim_nodes: negative window")
+	}
+	var pn, ps, pc *C.int32_t
+	if n > 0 { // &nodes[0] of an empty slice panics
+		nodes = make([]int32, n)
+		scores = make([]int32, n)
+		cands = make([]int32, n)
+		pn = (*C.int32_t)(unsafe.Pointer(&nodes[0]))
+		ps = (*C.int32_t)(unsafe.Pointer(&scores[0]))
+		pc = (*C.int32_t)(unsafe.Pointer(&cands[0]))
+	}
+	var raw [3]C.int64_t
+	t := C.kbhip_rank_victim_nodes(e.s, C.int32_t(task), boolI32(byScore), C.int32_t(victims), C.int64_t(first),
+		pn, ps, pc, C.int64_t(n), &raw[0])
+	if t < 0 {
+		return 0, nil, nil, nil, info, lastErr("rank_victim_nodes", C.int(t))
+	}
+	info = VictimWalkInfo{Head: raw[0] != 0, Rebuilt: raw[1] != 0, Launches: int64(raw[2])}
+	got := int64(t) - first
+	if got < 0 {
+		got = 0
+	}
+	if got > n {
+		got = n
+	}
+	return int64(t), nodes[:got], scores[:got], cands[:got], info, nil
+}
+
 // Op is one decision of a host-kept reclaim / preempt loop for ApplyOps.
 // Node is read for OpPipeline only (an eviction uses the pod's own node).
 type Op struct {

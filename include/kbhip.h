@@ -299,6 +299,51 @@ int64_t kbhip_rank_nodes(kb_session* s, int32_t task_id, int32_t by_score, int64
 int64_t kbhip_apply_ops(kb_session* s, const uint8_t* op, const int32_t* pod, const int32_t* node, int64_t n,
                         int64_t* out_launches);
 
+/* kbhip_rank_victim_nodes <- kbhip_rank_nodes' walk without the nodes on which
+ * validateVictims (preempt.go:355-370) rejects whatever ssn.Reclaimable /
+ * ssn.Preemptable answer.  The candidates of a node are its Running tasks
+ * with a Running node copy and a job (what KBHIP_OP_EVICT admits), narrowed by
+ * `victims` to what the caller's loop filters for:
+ *   KBHIP_VICTIMS_OTHER_QUEUES     jobs of queues other than the task's (reclaim.go)
+ *   KBHIP_VICTIMS_QUEUE_OTHER_JOBS the task's queue, jobs other than its own (preempt.go:104-127)
+ *   KBHIP_VICTIMS_SAME_JOB         the task's own job (preempt.go:151-181)
+ * A node stays in the walk when it has at least one candidate and the sum of
+ * the candidates' Resreq is not strictly below the task's InitResreq in all
+ * three resources at once (Resource.Less, the test validateVictims applies to
+ * the victims).  Victims are a subset of the candidates whatever the plugins
+ * and their order, so a node dropped here can yield no victim set that passes
+ * validateVictims: a host loop over this walk takes the decisions of the loop
+ * over kbhip_rank_nodes' walk, in the same order.
+ * Everything else is kbhip_rank_nodes' contract: the returned total and the
+ * window [first, first + cap) count kept nodes only; out_score is optional;
+ * first + cap <= 64 with cap > 0 is served by the fused top-64 sweep (the
+ * test applied by the lane that evaluates the node), anything else by the
+ * full device sort followed by a stable compaction of three launches.
+ * out_cands[i] (optional) = the candidate count of out_node[i].  out_info
+ * (optional, 3 entries) = whether the top-64 sweep served the call, whether
+ * the call (re)built the candidate table, the kernel launches it issued.
+ * The candidate table — per queue and node the candidates' count and Resreq
+ * sums, int64 [queues + 1][4][padded nodes] on the device — is built from the
+ * pods by the first call that needs it.  kbhip_apply_ops keeps it current (a
+ * KBHIP_OP_EVICT takes the pod off its node's entries inside that call's one
+ * node launch; the other operations change no candidate), so a host loop of
+ * rankings and operations never rebuilds it.  Every other call that changes
+ * pod statuses (the actions, kbhip_place_job and its asynchronous forms,
+ * kbhip_first_fit, the carry-overs) leaves it stale, and the next call here
+ * rebuilds and uploads it.  Design limit: a table above 512 MB is refused
+ * (KBHIP_EUNSUPPORTED, the message names the size).
+ * The call changes no node row, no counter of kbhip_walk_visits, and a task
+ * kbhip_fit_deltas would answer for stays answerable.  KBHIP_EINVAL: as
+ * kbhip_rank_nodes, and `victims` outside 1..3 or a task without a job;
+ * KBHIP_EUNSUPPORTED on node-sharded sessions; KBHIP_EDEVICE as
+ * kbhip_rank_nodes. */
+#define KBHIP_VICTIMS_OTHER_QUEUES 1      /* reclaim.go: Running tasks of jobs in other queues */
+#define KBHIP_VICTIMS_QUEUE_OTHER_JOBS 2  /* preempt.go:104-127: same queue, another job */
+#define KBHIP_VICTIMS_SAME_JOB 3          /* preempt.go:151-181: the task's own job */
+int64_t kbhip_rank_victim_nodes(kb_session* s, int32_t task_id, int32_t by_score, int32_t victims, int64_t first,
+                                int32_t* out_node, int32_t* out_score, int32_t* out_cands, int64_t cap,
+                                int64_t* out_info);
+
 /* Measurement hook (bench.py's sweep roofline): kbhip_sweep_scores' sweep
  * kernel for each given task, launched back to back on the session stream
  * with no copies in between; *out_mean_us = device time per launch (one

@@ -305,12 +305,17 @@ __global__ __launch_bounds__(kBlock) void k_apply_ops(NodeCols nc, DevTables t, 
     int64_t bc = 0, bm = 0, bg = 0;  // Backfilled
     int64_t zc = 0, zm = 0;          // non-zero requests
     int32_t dp = 0;                  // pod count
-    const int j1 = a.seg_off[i + 1];
-    for (int j = a.seg_off[i]; j < j1; ++j) {
+    int64_t ec = 0, em = 0, eg = 0;  // the evicted pods' Resreq and number (the candidate table)
+    int32_t en = 0;
+    const int j0 = a.seg_off[i], j1 = a.seg_off[i + 1];
+    for (int j = j0; j < j1; ++j) {
         const int32_t kc = a.kind_cls[j];
         const int op = kc & 3;
         if (op == 0) {
-            rc += a.req[3 * (size_t)j]; rm += a.req[3 * (size_t)j + 1]; rg += a.req[3 * (size_t)j + 2];
+            const int64_t c0 = a.req[3 * (size_t)j], c1 = a.req[3 * (size_t)j + 1], c2 = a.req[3 * (size_t)j + 2];
+            rc += c0; rm += c1; rg += c2;
+            ec += c0; em += c1; eg += c2;
+            en += 1;
             continue;
         }
         const TaskClass& c = t.classes[kc >> 2];
@@ -332,6 +337,35 @@ __global__ __launch_bounds__(kBlock) void k_apply_ops(NodeCols nc, DevTables t, 
     nc.rel_cpu[n] += rc; nc.rel_mem[n] += rm; nc.rel_gpu[n] += rg;
     if (bc | bm | bg) { nc.bf_cpu[n] += bc; nc.bf_mem[n] += bm; nc.bf_gpu[n] += bg; }
     if (dp | zc | zm) { nc.pods[n] += dp; nc.nzc[n] += zc; nc.nzm[n] += zm; }
+    // The victim-candidate table of kbhip_rank_victim_nodes, when the session
+    // holds a current one: an evicted pod stops being a candidate of its node.
+    // This lane owns column n of every row.  The total row takes the sums of
+    // the walk; each queue present among the segment's evictions takes its own
+    // sums, gathered in registers by one more pass over the segment per such
+    // queue (ascending), so every entry is read once and written once.
+    if (a.vict && en) {
+        const size_t np = (size_t)a.vict_npad;
+        int64_t* tot = a.vict + (size_t)a.vict_nq * 4 * np + n;
+        tot[0] -= en; tot[np] -= ec; tot[2 * np] -= em; tot[3 * np] -= eg;
+        for (int q = -1;;) {
+            int nq = INT32_MAX;
+            for (int j = j0; j < j1; ++j) {
+                const int qj = a.queue[j];
+                if ((a.kind_cls[j] & 3) == 0 && qj > q && qj < nq) nq = qj;
+            }
+            if (nq >= a.vict_nq) break;  // none left (the host validated the queues)
+            int64_t qc = 0, qm = 0, qg = 0;
+            int32_t qn = 0;
+            for (int j = j0; j < j1; ++j)
+                if ((a.kind_cls[j] & 3) == 0 && a.queue[j] == nq) {
+                    qc += a.req[3 * (size_t)j]; qm += a.req[3 * (size_t)j + 1]; qg += a.req[3 * (size_t)j + 2];
+                    qn += 1;
+                }
+            int64_t* row = a.vict + (size_t)nq * 4 * np + n;
+            row[0] -= qn; row[np] -= qc; row[2 * np] -= qm; row[3 * np] -= qg;
+            q = nq;
+        }
+    }
 }
 
 hipError_t launch_apply_ops(const NodeCols& nc, const DevTables& t, const ApplyOps& a, hipStream_t st) {
@@ -702,10 +736,47 @@ __device__ __forceinline__ void head_block_merge(uint64_t (*s_top)[64], uint64_t
     }
 }
 
-template <bool PLAIN>
-__global__ __launch_bounds__(kBlock) void k_rank_head(Conf cf, NodeCols nc, DevTables t, TaskClass c,
-                                                      const PopCtrl* ctrl, int by_score, uint64_t* lists,
-                                                      uint32_t* bcnt) {
+// The victim-candidate test of kbhip_rank_victim_nodes (VictArgs,
+// kbhip_internal.h) for node n: the candidate count and Resreq sums of the
+// call's mode, from at most two table rows of column n (coalesced over the
+// lanes of a wave) and the job's own list.
+struct Vict4 {
+    int64_t n, c, m, g;
+};
+__device__ __forceinline__ Vict4 vict_row(const VictArgs& v, int row, int n) {
+    const size_t np = (size_t)v.npad;
+    const int64_t* p = v.tab + (size_t)row * 4 * np + n;
+    return Vict4{p[0], p[np], p[2 * np], p[3 * np]};
+}
+__device__ __forceinline__ Vict4 vict_own(const VictArgs& v, int n) {
+    int lo = 0, hi = v.own_n;  // the first entry >= n
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (v.own_node[mid] < n) lo = mid + 1;
+        else hi = mid;
+    }
+    if (lo >= v.own_n || v.own_node[lo] != n) return Vict4{0, 0, 0, 0};
+    const int64_t* p = v.own_sum + 4 * (size_t)lo;
+    return Vict4{p[0], p[1], p[2], p[3]};
+}
+__device__ __forceinline__ Vict4 vict_cand(const VictArgs& v, int n) {
+    if (v.mode == 3) return vict_own(v, n);
+    Vict4 a, b;
+    if (v.mode == 1) { a = vict_row(v, v.nq, n); b = vict_row(v, v.q, n); }
+    else { a = vict_row(v, v.q, n); b = vict_own(v, n); }
+    return Vict4{a.n - b.n, a.c - b.c, a.m - b.m, a.g - b.g};
+}
+__device__ __forceinline__ bool vict_keep(const VictArgs& v, const Vict4& a) {
+    return a.n > 0 && !(a.c < v.rc && a.m < v.rm && a.g < v.rg);
+}
+
+// FILT: the lane that evaluates a node also loads the node's candidate sums
+// (before the evaluation: the loads run under it) and zeroes its key when the
+// node fails the test; without FILT v is never read.
+template <bool PLAIN, bool FILT>
+__device__ __forceinline__ void rank_head(const Conf& cf, const NodeCols& nc, const DevTables& t, const TaskClass& c,
+                                          const PopCtrl* ctrl, int by_score, uint64_t* lists, uint32_t* bcnt,
+                                          const VictArgs& v) {
     __shared__ uint64_t s_top[kHeadWaves][64];
     __shared__ uint32_t s_cnt[kHeadWaves];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -720,6 +791,10 @@ __global__ __launch_bounds__(kBlock) void k_rank_head(Conf cf, NodeCols nc, DevT
     for (; b < nc.n; b += stride) {
         const int n = b + lane;
         uint64_t k = 0;
+        Vict4 va{};
+        if constexpr (FILT) {
+            if (n < nc.n) va = vict_cand(v, n);
+        }
         if constexpr (PLAIN) {
             SweepIn nxt{};
             if (n + stride < nc.n) nxt = sweep_in(nc, n + stride);
@@ -748,6 +823,9 @@ __global__ __launch_bounds__(kBlock) void k_rank_head(Conf cf, NodeCols nc, DevT
                 k = eval_first_fit(cf, c, t, nc, n);
             }
         }
+        if constexpr (FILT) {
+            if (!vict_keep(v, va)) k = 0;  // (lanes past the last node: va is zero, k already is)
+        }
         cnt += (uint32_t)__popcll(__ballot(k != 0));
         if (__ballot(k > readlane64(top, 63)) == 0) continue;  // uniform: nothing enters the top 64
         top = wave_merge_desc(top, wave_sort_desc(k));
@@ -760,6 +838,19 @@ __global__ __launch_bounds__(kBlock) void k_rank_head(Conf cf, NodeCols nc, DevT
         for (int w = 0; w < kHeadWaves; ++w) tot += s_cnt[w];
         bcnt[blockIdx.x] = tot;
     }
+}
+
+template <bool PLAIN>
+__global__ __launch_bounds__(kBlock) void k_rank_head(Conf cf, NodeCols nc, DevTables t, TaskClass c,
+                                                      const PopCtrl* ctrl, int by_score, uint64_t* lists,
+                                                      uint32_t* bcnt) {
+    rank_head<PLAIN, false>(cf, nc, t, c, ctrl, by_score, lists, bcnt, VictArgs{});
+}
+template <bool PLAIN>
+__global__ __launch_bounds__(kBlock) void k_rank_head_vict(Conf cf, NodeCols nc, DevTables t, TaskClass c,
+                                                           const PopCtrl* ctrl, int by_score, uint64_t* lists,
+                                                           uint32_t* bcnt, VictArgs v) {
+    rank_head<PLAIN, true>(cf, nc, t, c, ctrl, by_score, lists, bcnt, v);
 }
 
 __global__ __launch_bounds__(kBlock) void k_rank_head_merge(const uint64_t* lists, const uint32_t* bcnt, int nblk,
@@ -805,6 +896,96 @@ hipError_t launch_rank_head(const Conf& cf, const NodeCols& nc, const DevTables&
                            bcnt);
     hipLaunchKernelGGL(k_rank_head_merge, dim3(1), dim3(kBlock), 0, st, (const uint64_t*)lists,
                        (const uint32_t*)bcnt, grid, out);
+    return hipGetLastError();
+}
+
+hipError_t launch_rank_head_vict(const Conf& cf, const NodeCols& nc, const DevTables& t, const TaskClass& c,
+                                 const PopCtrl* ctrl, int by_score, const VictArgs& v, uint64_t* scratch,
+                                 hipStream_t st) {
+    uint64_t* out = scratch;
+    uint64_t* lists = scratch + kTopK + 1;
+    uint32_t* bcnt = reinterpret_cast<uint32_t*>(lists + (size_t)kHeadMaxBlocks * 64);
+    const int grid = rank_head_blocks(nc.n);
+    if (by_score && !c.aff && c.ipa_n == 0)
+        hipLaunchKernelGGL((k_rank_head_vict<true>), dim3(grid), dim3(kBlock), 0, st, cf, nc, t, c, ctrl, by_score,
+                           lists, bcnt, v);
+    else
+        hipLaunchKernelGGL((k_rank_head_vict<false>), dim3(grid), dim3(kBlock), 0, st, cf, nc, t, c, ctrl, by_score,
+                           lists, bcnt, v);
+    hipLaunchKernelGGL(k_rank_head_merge, dim3(1), dim3(kBlock), 0, st, (const uint64_t*)lists,
+                       (const uint32_t*)bcnt, grid, out);
+    return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------
+// The full walk of kbhip_rank_victim_nodes: the sorted keys of the ranking
+// above (count[0] of them, best first) without the nodes that fail the victim
+// test, order kept.  Block b takes keys [b kBlock, (b + 1) kBlock):
+//   k_vict_count    its survivors -> blk[b] (block 0 also zeroes blk[nblk])
+//   k_rank_scan     exclusive scan of blk[0 .. nblk]: blk[nblk] = the total
+//   k_vict_scatter  survivor i of the block (wave ballots, earlier waves'
+//                   counts) -> out_keys / out_cands[blk[b] + i]
+// The launch boundaries order them: no block waits for another.  The test is
+// evaluated in both passes (per key at most two table rows of its node,
+// gathered in walk order, and the own list) instead of a flag array written
+// and read back.
+// ---------------------------------------------------------------------------
+__device__ __forceinline__ bool vict_key_keep(const uint64_t* sorted, const uint32_t* count, int n_nodes,
+                                              const VictArgs& v, int i, uint64_t* k_out, Vict4* a_out) {
+    const int cnt = (int)count[0] < n_nodes ? (int)count[0] : n_nodes;
+    if (i >= cnt) return false;
+    const uint64_t k = sorted[i];
+    const int n = key_idx(k);
+    if (!k || n < 0 || n >= n_nodes) return false;
+    const Vict4 a = vict_cand(v, n);
+    *k_out = k;
+    *a_out = a;
+    return vict_keep(v, a);
+}
+__global__ __launch_bounds__(kBlock) void k_vict_count(const uint64_t* sorted, const uint32_t* count, int n_nodes,
+                                                       VictArgs v, uint32_t* blk) {
+    __shared__ uint32_t s_cnt[kBlock / 64];
+    uint64_t k;
+    Vict4 a;
+    const bool keep = vict_key_keep(sorted, count, n_nodes, v, blockIdx.x * kBlock + threadIdx.x, &k, &a);
+    const uint32_t c = (uint32_t)__popcll(__ballot(keep));
+    if ((threadIdx.x & 63) == 0) s_cnt[threadIdx.x >> 6] = c;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        uint32_t tot = 0;
+        for (int w = 0; w < kBlock / 64; ++w) tot += s_cnt[w];
+        blk[blockIdx.x] = tot;
+        if (blockIdx.x == 0) blk[gridDim.x] = 0;
+    }
+}
+__global__ __launch_bounds__(kBlock) void k_vict_scatter(const uint64_t* sorted, const uint32_t* count, int n_nodes,
+                                                         VictArgs v, const uint32_t* blk, uint64_t* out_keys,
+                                                         int32_t* out_cands) {
+    __shared__ uint32_t s_cnt[kBlock / 64];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    uint64_t k = 0;
+    Vict4 a{};
+    const bool keep = vict_key_keep(sorted, count, n_nodes, v, blockIdx.x * kBlock + threadIdx.x, &k, &a);
+    const uint64_t m = __ballot(keep);
+    if (lane == 0) s_cnt[wave] = (uint32_t)__popcll(m);
+    __syncthreads();
+    if (!keep) return;
+    uint32_t pos = blk[blockIdx.x] + (uint32_t)__popcll(m & (lane ? (~0ull >> (64 - lane)) : 0ull));
+    for (int w = 0; w < wave; ++w) pos += s_cnt[w];
+    if (pos >= (uint32_t)n_nodes) return;  // (the survivors are a subset of the n_nodes keys)
+    out_keys[pos] = k;
+    out_cands[pos] = (int32_t)a.n;
+}
+
+int vict_blocks(int n_nodes) { return n_nodes > 0 ? (n_nodes + kBlock - 1) / kBlock : 1; }
+
+hipError_t launch_vict_compact(const uint64_t* sorted, const uint32_t* count, int n_nodes, const VictArgs& v,
+                               uint32_t* blk, uint64_t* out_keys, int32_t* out_cands, hipStream_t st) {
+    const int nblk = vict_blocks(n_nodes);
+    hipLaunchKernelGGL(k_vict_count, dim3(nblk), dim3(kBlock), 0, st, sorted, count, n_nodes, v, blk);
+    hipLaunchKernelGGL(k_rank_scan, dim3(1), dim3(1024), 0, st, blk, nblk + 1);
+    hipLaunchKernelGGL(k_vict_scatter, dim3(nblk), dim3(kBlock), 0, st, sorted, count, n_nodes, v,
+                       (const uint32_t*)blk, out_keys, out_cands);
     return hipGetLastError();
 }
 

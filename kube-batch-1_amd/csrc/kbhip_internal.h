@@ -99,6 +99,39 @@ int rank_head_blocks(int n_nodes);  // the sweep's grid
 size_t rank_head_words();
 hipError_t launch_rank_head(const Conf& cf, const NodeCols& nc, const DevTables& t, const TaskClass& c,
                             const PopCtrl* ctrl, int by_score, uint64_t* scratch, hipStream_t st);
+// kbhip_rank_victim_nodes: the walk without the nodes validateVictims
+// (preempt.go:355-370) rejects whatever the plugins answer.  The candidate
+// table (device pointers) holds per queue q and node n the Running tasks with
+// a Running node copy and a job: tab[(q * 4 + k) * npad + n], k = 0 their
+// count, 1..3 the sum of their Resreq (cpu, memory, gpu); row nq is the total
+// over the queues.  A lane that owns a node reads at most two rows of it.
+// mode (KBHIP_VICTIMS_*): 1 total - row q, 2 row q - the job's own, 3 the
+// job's own; the job's own candidates per node come as a list of distinct
+// nodes in ascending order (own_node) with their four sums (own_sum[4 i ..]),
+// found by binary search.  A node is kept when its candidate count is > 0 and
+// the sum is not strictly below (rc, rm, rg) — the task's InitResreq — in all
+// three resources.
+struct VictArgs {
+    const int64_t* tab;
+    const int32_t* own_node;
+    const int64_t* own_sum;
+    int32_t npad, nq, q, mode, own_n;
+    int64_t rc, rm, rg;
+};
+// The filtered head: launch_rank_head with the test above applied by the lane
+// that evaluates the node (scratch as there; the count is the kept nodes').
+hipError_t launch_rank_head_vict(const Conf& cf, const NodeCols& nc, const DevTables& t, const TaskClass& c,
+                                 const PopCtrl* ctrl, int by_score, const VictArgs& v, uint64_t* scratch,
+                                 hipStream_t st);
+// The filtered full walk: a stable compaction of launch_rank_sorted's /
+// launch_rank_radix's output (sorted, *count keys) in three launches — per
+// block of kBlock keys the survivors' count (blk[b]), k_rank_scan over blk
+// (blk[nblk] = the total afterwards), a scatter of the survivors and their
+// candidate counts in order.  blk holds vict_blocks(n) + 1 words; out_keys /
+// out_cands n_nodes entries.
+int vict_blocks(int n_nodes);
+hipError_t launch_vict_compact(const uint64_t* sorted, const uint32_t* count, int n_nodes, const VictArgs& v,
+                               uint32_t* blk, uint64_t* out_keys, int32_t* out_cands, hipStream_t st);
 // One session's ranking request in a batched launch (what-if sessions).
 struct RankDesc {
     Conf cf;
@@ -139,6 +172,11 @@ struct ApplyOps {
     const int32_t* kind_cls;
     const int64_t* req;
     int n_seg;
+    // the victim-candidate table (VictArgs above) while the session holds a current one, else null: an
+    // eviction takes the pod's Resreq and 1 off its queue's row (queue[j], evictions only) and off the total row
+    const int32_t* queue;
+    int64_t* vict;
+    int32_t vict_npad, vict_nq;
 };
 // One lane per segment, as many blocks as the segments need (one launch whatever the batch holds).
 hipError_t launch_apply_ops(const NodeCols& nc, const DevTables& t, const ApplyOps& a, hipStream_t st);

@@ -901,6 +901,7 @@ int place_job(Session& S, const int32_t* ids, int n, int gang_mode, int min_avai
     int done = 0, stop = KBHIP_STOP_ALL;
     check_task_ids(S, ids, n);
     S.fit_task = -1;
+    vict_stale(S);
     while (done < n) {
         const int cls0 = S.pods[ids[done]].cls;
         int m = 1;
@@ -1111,6 +1112,7 @@ int place_job_wait(Session& S, int64_t ticket, int32_t* out_node, uint8_t* out_k
     PopTicket t = std::move(S.tickets.front());
     S.tickets.pop_front();
     S.fit_task = -1;
+    vict_stale(S);
     const int n = (int)t.ids.size();
     bool sync = !t.collected;
     if (t.collected) {

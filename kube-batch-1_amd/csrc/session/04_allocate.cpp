@@ -431,6 +431,7 @@ struct AllocateAction {
 
 void allocate_run(Session& S) {
     S.fit_task = -1;
+    vict_stale(S);
     AllocateAction a(S);
     a.run();
 }
@@ -453,6 +454,7 @@ void first_fit(Session& S, const int32_t* ids, int n, int32_t* out_node) {
             throw Error(KBHIP_EINVAL, "task id is not a pending task of the session");
     std::fill(out_node, out_node + n, -1);
     S.fit_task = -1;
+    vict_stale(S);
     ov_quiesce(S);
     Framework F(S);
     F.compile_orders();

@@ -299,6 +299,7 @@ int device_count() {
 // New pods, node and PodGroup changes: kbhip_session_carry_snapshot.
 void session_carry(Session& S, const int32_t* ev_pod, const uint8_t* ev, int64_t n_ev) {
     S.model_gen++;  // per-pod caches of the host model (Session::pod_queue) are rebuilt
+    vict_stale(S);
     // every node's row is recomputed on the host (a shard's host model holds
     // all of them); this device's rows [lo, lo + Nl) are compared and uploaded
     const int N = (int)S.h_alloc.size(), Nl = S.nc.n, lo = S.nc.base, P = (int)S.pods.size();

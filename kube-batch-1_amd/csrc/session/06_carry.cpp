@@ -194,6 +194,7 @@ void carry_snapshot(kb_session* ks, const kbs::Snapshot& s, const int32_t* old_p
     ov_quiesce(S);
     HIPCHK(hipStreamSynchronize(S.stream));
     S.model_gen++;  // jobs are renumbered: per-pod caches of the host model are rebuilt
+    vict_stale(S);
     if (!carry_fast_ok(S, s, v, old_pod, old_node)) {
         reopen_in_place(ks, s);
         return;

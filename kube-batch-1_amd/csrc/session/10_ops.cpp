@@ -120,9 +120,12 @@ static int launch_node_ops(Session& S, const vector<NodeOp>& ops) {
         seg_cnt[sg]++;
     }
     const size_t D = seg_node.size();
-    // staging layout (8-byte aligned parts): req[3 M] | seg_node[D] | seg_off[D + 1] | kind_cls[M]
+    const bool vict = S.vict_live && S.b_vict.p;  // the victim-candidate table follows the evictions
+    // staging layout (8-byte aligned parts): req[3 M] | seg_node[D] | seg_off[D + 1] | kind_cls[M] | queue[M]
+    // (queue: only with a live victim-candidate table)
     const size_t o_req = 0, o_node = o_req + 3 * M * sizeof(int64_t), o_off = o_node + align8(D * sizeof(int32_t)),
-                 o_kc = o_off + align8((D + 1) * sizeof(int32_t)), bytes = o_kc + align8(M * sizeof(int32_t));
+                 o_kc = o_off + align8((D + 1) * sizeof(int32_t)), o_q = o_kc + align8(M * sizeof(int32_t)),
+                 bytes = o_q + (vict ? align8(M * sizeof(int32_t)) : 0);
     if (!S.ev_ops) HIPCHK(hipEventCreateWithFlags(&S.ev_ops, hipEventDisableTiming));
     else HIPCHK(hipEventSynchronize(S.ev_ops));  // the previous call's copy has read the staging
     if (S.h_ops_cap < bytes) {
@@ -140,6 +143,7 @@ static int launch_node_ops(Session& S, const vector<NodeOp>& ops) {
     int32_t* h_node = (int32_t*)(S.h_ops + o_node);
     int32_t* h_off = (int32_t*)(S.h_ops + o_off);
     int32_t* h_kc = (int32_t*)(S.h_ops + o_kc);
+    int32_t* h_q = vict ? (int32_t*)(S.h_ops + o_q) : nullptr;
     int32_t run = 0;
     for (size_t d = 0; d < D; ++d) {
         h_node[d] = seg_node[d] - S.nc.base;  // (one-GPU sessions: base 0)
@@ -152,12 +156,14 @@ static int launch_node_ops(Session& S, const vector<NodeOp>& ops) {
         const int32_t j = seg_cnt[S.ops_seg[o.node]]++;
         h_kc[j] = o.kind | (o.cls << 2);
         h_req[3 * (size_t)j] = o.req.c; h_req[3 * (size_t)j + 1] = o.req.m; h_req[3 * (size_t)j + 2] = o.req.g;
+        if (h_q) h_q[j] = o.queue;
     }
     uint8_t* d = (uint8_t*)S.b_ops.p;
     HIPCHK(hipMemcpyAsync(d, S.h_ops, bytes, hipMemcpyHostToDevice, S.stream));
     HIPCHK(hipEventRecord(S.ev_ops, S.stream));
     ApplyOps a{(const int32_t*)(d + o_node), (const int32_t*)(d + o_off), (const int32_t*)(d + o_kc),
-               (const int64_t*)(d + o_req), (int)D};
+               (const int64_t*)(d + o_req), (int)D, vict ? (const int32_t*)(d + o_q) : nullptr,
+               vict ? (int64_t*)S.b_vict.p : nullptr, S.nc.npad, (int32_t)S.queues.size()};
     HIPCHK(launch_apply_ops(S.nc, S.tab, a, S.stream));
     return 1;
 }
@@ -170,11 +176,18 @@ int64_t apply_ops(Session& S, const uint8_t* op, const int32_t* pod, const int32
     if (n > (int64_t)INT32_MAX)  // (the segment offsets on the device are 32-bit)
         throw Error(KBHIP_EINVAL, "kbhip_apply_ops: n exceeds 2^31 - 1 operations");
     validate_ops(S, op, pod, node, n);
+    struct VictGuard {  // a batch that fails part way leaves the victim-candidate table to be rebuilt
+        Session& S;
+        bool done = false;
+        ~VictGuard() { if (!done) S.vict_live = false; }
+    } vict_guard{S};
     ov_quiesce(S);  // device work outside the batched pops' chain follows
     vector<NodeOp> ops;
     ops.reserve((size_t)n);
     apply_ops_model(S, op, pod, node, n, ops);
-    int launches = launch_node_ops(S, ops);
+    int launches = launch_node_ops(S, ops);  // (a live victim-candidate table: its evictions in the same launch)
+    if (S.vict_live) vict_apply_evictions(S, ops);
+    vict_guard.done = true;
     launches += flush_tables(S);  // the evictions' / unevicts' predicate-target changes
     commit_marks(S, op, pod, n);
     if (out_launches) *out_launches = launches;

@@ -560,6 +560,7 @@ struct EvictAction {
 
 void evict_run(Session& S, bool preempt) {
     S.fit_task = -1;
+    vict_stale(S);
     EvictAction a(S);
     if (preempt) a.preempt_action();
     else a.reclaim_action();

@@ -1,0 +1,267 @@
+// kbhip session, part 12: the victim-candidate table and the pruned node walk (kbhip_rank_victim_nodes)
+#include "framework.h"
+
+namespace kbhip {
+
+namespace {
+
+constexpr size_t kVictMaxBytes = (size_t)512 << 20;  // the table's design limit (include/kbhip.h)
+
+size_t vict_tab_words(const Session& S) { return (S.queues.size() + 1) * 4 * (size_t)S.nc.npad; }
+
+// The table from the host model and its upload: a parallel pass over the pods
+// by pod ranges (as EvictAction::build_node_tasks), each range into a table of
+// its own; the ranges' tables are then summed by node ranges, which also
+// gives the total row.  The ranges are as many as keep the partial tables
+// within the table's own size limit.
+void vict_build(Session& S) {
+    const size_t Q = S.queues.size(), np = (size_t)S.nc.npad, words = vict_tab_words(S), bytes = words * sizeof(int64_t);
+    if (bytes > kVictMaxBytes)
+        throw Error(KBHIP_EUNSUPPORTED, "kbhip_rank_victim_nodes: the victim-candidate table of " + std::to_string(Q) +
+                                            " queues x " + std::to_string(np) + " nodes takes " +
+                                            std::to_string(bytes >> 20) + " MB, above the 512 MB limit");
+    const int P = (int)S.pods.size(), N = S.n_total;
+    int nth = P < (1 << 16) ? 1 : host_threads();
+    nth = (int)std::max<size_t>(1, std::min<size_t>((size_t)nth, kVictMaxBytes / std::max<size_t>(bytes, 1)));
+    S.vict_tab.assign(words, 0);
+    vector<vector<int64_t>> part(nth - 1);
+    run_ranges(nth, [&](int r) {
+        if (r > 0) part[r - 1].assign(words, 0);
+        int64_t* tab = r > 0 ? part[r - 1].data() : S.vict_tab.data();
+        const auto [b, e] = range_of(P, r, nth);
+        for (int i = b; i < e; ++i) {
+            const HPod& p = S.pods[i];
+            if (!vict_candidate(S, p)) continue;
+            const int q = S.jobs[p.job].queue;
+            if (q < 0 || q >= (int)Q) continue;
+            int64_t* row = tab + (size_t)q * 4 * np + p.node;
+            row[0] += 1; row[np] += p.req.c; row[2 * np] += p.req.m; row[3 * np] += p.req.g;
+        }
+    });
+    const int nsum = nth > 1 || N >= (1 << 16) ? std::min(host_threads(), std::max(1, N / 4096)) : 1;
+    run_ranges(nsum, [&](int r) {
+        const auto [b, e] = range_of(N, r, nsum);
+        int64_t* tab = S.vict_tab.data();
+        for (size_t qk = 0; qk < Q * 4; ++qk) {
+            int64_t* row = tab + qk * np;
+            for (const auto& pt : part) {
+                const int64_t* src = pt.data() + qk * np;
+                for (int n = b; n < e; ++n) row[n] += src[n];
+            }
+            int64_t* tot = tab + (Q * 4 + qk % 4) * np;
+            for (int n = b; n < e; ++n) tot[n] += row[n];
+        }
+    });
+    if (S.b_vict.cap < bytes || !S.b_vict.p) S.b_vict.alloc<int64_t>(words);
+    HIPCHK(hipMemcpyAsync(S.b_vict.p, S.vict_tab.data(), bytes, hipMemcpyHostToDevice, S.stream));
+    HIPCHK(hipStreamSynchronize(S.stream));  // the pageable source is read by then
+    S.vict_live = true;
+}
+
+// The candidate tasks of job jb per node: distinct nodes ascending, four sums each.
+void vict_own_list(const Session& S, int jb, vector<int32_t>& node, vector<int64_t>& sum) {
+    node.clear();
+    sum.clear();
+    vector<std::pair<int32_t, int32_t>> on;  // (node, pod)
+    for (int t : S.jobs[jb].tasks)
+        if (vict_candidate(S, S.pods[t])) on.emplace_back(S.pods[t].node, t);
+    std::sort(on.begin(), on.end());
+    for (const auto& [n, t] : on) {
+        if (node.empty() || node.back() != n) {
+            node.push_back(n);
+            sum.insert(sum.end(), 4, 0);
+        }
+        int64_t* s = &sum[sum.size() - 4];
+        const R3& r = S.pods[t].req;
+        s[0] += 1; s[1] += r.c; s[2] += r.m; s[3] += r.g;
+    }
+}
+
+// vict_cand of kbhip_evict.hip on the host copy: the candidate count of node n
+int64_t vict_count_host(const Session& S, int mode, int q, const vector<int32_t>& own_node,
+                        const vector<int64_t>& own_sum, int n) {
+    const size_t np = (size_t)S.nc.npad, Q = S.queues.size();
+    int64_t own = 0;
+    if (mode != 1) {
+        const auto it = std::lower_bound(own_node.begin(), own_node.end(), n);
+        if (it != own_node.end() && *it == n) own = own_sum[4 * (size_t)(it - own_node.begin())];
+    }
+    if (mode == 3) return own;
+    if (mode == 1) return S.vict_tab[Q * 4 * np + n] - S.vict_tab[(size_t)q * 4 * np + n];
+    return S.vict_tab[(size_t)q * 4 * np + n] - own;
+}
+
+}  // namespace
+
+void vict_apply_evictions(Session& S, const vector<NodeOp>& ops) {
+    const size_t np = (size_t)S.nc.npad, Q = S.queues.size();
+    for (const NodeOp& o : ops) {
+        if (o.kind != 0) continue;
+        if (o.queue < 0 || o.queue >= (int)Q || o.node < 0 || o.node >= S.nc.npad) { S.vict_live = false; return; }
+        for (size_t row : {(size_t)o.queue, Q}) {
+            int64_t* p = S.vict_tab.data() + row * 4 * np + o.node;
+            p[0] -= 1; p[np] -= o.req.c; p[2 * np] -= o.req.m; p[3 * np] -= o.req.g;
+        }
+    }
+}
+
+// kbhip_rank_nodes' walk (09_rank.cpp) without the nodes whose victim
+// candidates of `mode` are none, or together strictly short of the task's
+// InitResreq in all three resources.  The head (first + cap <= kTopK) is one
+// filtered sweep (launch_rank_head_vict) with the candidate counts of the
+// returned nodes taken from the host copy of the table; anything else is the
+// actions' full sort followed by a stable compaction (launch_vict_compact), of
+// which the count and then the window asked for are copied back.
+int64_t rank_victim_nodes_abi(Session& S, int pod, bool by_score, int mode, int64_t first, int32_t* out_node,
+                              int32_t* out_score, int32_t* out_cands, int64_t cap, int64_t* out_info) {
+    if (pod < 0 || pod >= (int)S.pods.size() || S.pods[pod].cls < 0)
+        throw Error(KBHIP_EINVAL, "task id has no task class (not a pending task of the session)");
+    if (S.pods[pod].status != Pending)
+        throw Error(KBHIP_EINVAL, "kbhip_rank_victim_nodes: the task is not Pending (the session placed it)");
+    const int jb = S.pods[pod].job;
+    if (jb < 0 || S.jobs[jb].queue < 0 || S.jobs[jb].queue >= (int)S.queues.size())
+        throw Error(KBHIP_EINVAL, "kbhip_rank_victim_nodes: the task has no job");
+    if (S.world != 1) throw Error(KBHIP_EUNSUPPORTED, "kbhip_rank_victim_nodes on a node-sharded session");
+    ov_quiesce(S);
+    const int cls = S.pods[pod].cls, N = S.nc.n;
+    const bool rebuilt = !S.vict_live;
+    if (rebuilt) vict_build(S);
+    vector<int32_t> own_node;
+    vector<int64_t> own_sum;
+    if (mode != KBHIP_VICTIMS_OTHER_QUEUES) vict_own_list(S, jb, own_node, own_sum);
+    const size_t own_n = own_node.size(), own_bytes = own_n * (4 * sizeof(int64_t) + sizeof(int32_t));
+    if (own_n) {  // sums, then nodes, in one copy (the previous call's copy ended with that call)
+        if (S.h_vict_own_cap < own_bytes) {
+            if (S.h_vict_own) MemPool::get().give(MemPool::kPinned, S.h_vict_own, S.h_vict_own_cap, S.device);
+            S.h_vict_own = nullptr;
+            S.h_vict_own_cap = 0;
+            S.h_vict_own = (uint8_t*)MemPool::get().take(MemPool::kPinned, std::max<size_t>(2 * own_bytes, 4096),
+                                                          &S.h_vict_own_cap);
+        }
+        if (S.vict_own_cap < own_bytes) {
+            HIPCHK(hipStreamSynchronize(S.stream));
+            S.vict_own_cap = std::max<size_t>(2 * own_bytes, 4096);
+            S.b_vict_own.alloc<uint8_t>(S.vict_own_cap);
+        }
+        std::memcpy(S.h_vict_own, own_sum.data(), own_n * 4 * sizeof(int64_t));
+        std::memcpy(S.h_vict_own + own_n * 4 * sizeof(int64_t), own_node.data(), own_n * sizeof(int32_t));
+        HIPCHK(hipMemcpyAsync(S.b_vict_own.p, S.h_vict_own, own_bytes, hipMemcpyHostToDevice, S.stream));
+    }
+    const R3& ireq = S.pods[pod].ireq;
+    const uint8_t* d_own = (const uint8_t*)S.b_vict_own.p;
+    const VictArgs v{(const int64_t*)S.b_vict.p,
+                     own_n ? (const int32_t*)(d_own + own_n * 4 * sizeof(int64_t)) : nullptr,
+                     own_n ? (const int64_t*)d_own : nullptr,
+                     S.nc.npad, (int32_t)S.queues.size(), S.jobs[jb].queue, mode, (int32_t)own_n,
+                     ireq.c, ireq.m, ireq.g};
+    const TaskClass& c = S.classes[cls];
+    const bool ipa = by_score && c.ipa_n > 0;
+    const uint64_t* keys = nullptr;
+    const int32_t* cands = nullptr;
+    int64_t total = 0, n_keys = 0, launches = flush_tables(S);  // evictions / unevicts so far change pod-affinity predicates
+    const bool head = cap > 0 && first <= kTopK && cap <= kTopK - first;
+    if (!S.h_vict_out || S.h_vict_out_cap < ((size_t)N + 2) * sizeof(int32_t)) {
+        if (S.h_vict_out) MemPool::get().give(MemPool::kPinned, S.h_vict_out, S.h_vict_out_cap, S.device);
+        S.h_vict_out = nullptr;
+        S.h_vict_out = (int32_t*)MemPool::get().take(MemPool::kPinned, ((size_t)N + 2) * sizeof(int32_t),
+                                                     &S.h_vict_out_cap);
+    }
+    if (head) {
+        if (!S.b_rank_head.p) S.b_rank_head.alloc<uint64_t>(rank_head_words());
+        if (!S.h_rank_head)
+            S.h_rank_head = (uint64_t*)MemPool::get().take(MemPool::kPinned, (size_t)(kTopK + 1) * sizeof(uint64_t),
+                                                           &S.h_rank_head_cap);
+        ctrl_setup(S, 1, &cls, 0, 0, 0, 0, -1, 0);
+        if (ipa) HIPCHK(launch_ipa_minmax(S.nc, S.tab, S.d_ctrl, 0, S.stream));
+        HIPCHK(launch_rank_head_vict(S.conf, S.nc, S.tab, c, S.d_ctrl, by_score ? 1 : 0, v,
+                                     (uint64_t*)S.b_rank_head.p, S.stream));
+        HIPCHK(hipMemcpyAsync(S.h_rank_head, S.b_rank_head.p, (size_t)(kTopK + 1) * sizeof(uint64_t),
+                              hipMemcpyDeviceToHost, S.stream));
+        HIPCHK(hipStreamSynchronize(S.stream));
+        total = (int64_t)S.h_rank_head[kTopK];
+        n_keys = first < total ? std::min(cap, total - first) : 0;
+        keys = S.h_rank_head + first;
+        for (int64_t i = 0; i < n_keys; ++i)
+            S.h_vict_out[1 + i] = (int32_t)vict_count_host(S, mode, v.q, own_node, own_sum, key_idx(keys[i]));
+        cands = S.h_vict_out + 1;
+        launches += 1 + (ipa ? 1 : 0) + 2;  // the control block, the inter-pod prepass, sweep + merge
+    } else {
+        rank_launch(S, cls, by_score);
+        if (!S.b_vict_keys.p) {
+            S.b_vict_keys.alloc<uint64_t>(std::max(N, 1));
+            S.b_vict_cands.alloc<int32_t>(std::max(N, 1));
+            S.b_vict_blk.alloc<uint32_t>((size_t)vict_blocks(N) + 1);
+        }
+        HIPCHK(launch_vict_compact((const uint64_t*)S.b_rank_sorted.p, (const uint32_t*)S.b_rank_cnt.p, N, v,
+                                   (uint32_t*)S.b_vict_blk.p, (uint64_t*)S.b_vict_keys.p,
+                                   (int32_t*)S.b_vict_cands.p, S.stream));
+        HIPCHK(hipMemcpyAsync(S.h_rank, S.b_rank_cnt.p, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, S.stream));
+        HIPCHK(hipMemcpyAsync(S.h_vict_out, (const uint32_t*)S.b_vict_blk.p + vict_blocks(N), sizeof(uint32_t),
+                              hipMemcpyDeviceToHost, S.stream));
+        HIPCHK(hipStreamSynchronize(S.stream));
+        if (S.h_rank[0] >> 32)
+            throw Error(KBHIP_EDEVICE, "rank_victim_nodes: node score outside the class score range");
+        total = (int64_t)(uint32_t)S.h_vict_out[0];
+        n_keys = first < total ? std::min(cap, total - first) : 0;
+        if (n_keys > 0) {
+            HIPCHK(hipMemcpyAsync(S.h_rank + 1, (const uint64_t*)S.b_vict_keys.p + first,
+                                  (size_t)n_keys * sizeof(uint64_t), hipMemcpyDeviceToHost, S.stream));
+            HIPCHK(hipMemcpyAsync(S.h_vict_out + 1, (const int32_t*)S.b_vict_cands.p + first,
+                                  (size_t)n_keys * sizeof(int32_t), hipMemcpyDeviceToHost, S.stream));
+            HIPCHK(hipStreamSynchronize(S.stream));
+        }
+        keys = S.h_rank + 1;
+        cands = S.h_vict_out + 1;
+        // rank_launch's own launches (11_evict.cpp): the control block, the inter-pod prepass, then the
+        // counting sort's three kernels or the key sweep and four radix passes of three; then the compaction's three
+        auto sr = S.class_srange[cls];
+        if (ipa) {
+            const int64_t w = 10 * (int64_t)S.conf.w_pa * S.conf.score_mult;
+            sr.first += std::min<int64_t>(0, w);
+            sr.second += std::max<int64_t>(0, w);
+        }
+        const bool counting = !S.force_radix && sr.second - sr.first < 256 && sr.first >= INT32_MIN &&
+                              sr.second <= INT32_MAX;
+        launches += 1 + (ipa ? 1 : 0) + (counting ? 3 : 13) + 3;
+    }
+    for (int64_t i = 0; i < n_keys; ++i) {
+        out_node[i] = key_idx(keys[i]);
+        if (out_score) out_score[i] = by_score ? key_score(keys[i]) : 0;
+        if (out_cands) out_cands[i] = cands[i];
+    }
+    if (out_info) {
+        out_info[0] = head ? 1 : 0;
+        out_info[1] = rebuilt ? 1 : 0;
+        out_info[2] = launches;
+    }
+    S.stats.sweeps++;
+    return total;
+}
+
+}  // namespace kbhip
+
+using namespace kbhip;
+
+extern "C" {
+
+int64_t kbhip_rank_victim_nodes(kb_session* s, int32_t task_id, int32_t by_score, int32_t victims, int64_t first,
+                                int32_t* out_node, int32_t* out_score, int32_t* out_cands, int64_t cap,
+                                int64_t* out_info) {
+    ABI_GUARD_S(s, {
+        if (!s) throw kbhip::Error(KBHIP_EINVAL, "null session");
+        if (first < 0 || cap < 0 || (cap > 0 && !out_node))
+            throw kbhip::Error(KBHIP_EINVAL,
+                               "kbhip_rank_victim_nodes: negative first or cap, or null out_node with cap > 0");
+        if (by_score != 0 && by_score != 1)
+            throw kbhip::Error(KBHIP_EINVAL, "kbhip_rank_victim_nodes: by_score is 0 or 1");
+        if (victims < KBHIP_VICTIMS_OTHER_QUEUES || victims > KBHIP_VICTIMS_SAME_JOB)
+            throw kbhip::Error(KBHIP_EINVAL, "kbhip_rank_victim_nodes: victims is one of KBHIP_VICTIMS_* (1..3)");
+        if (s->s.encode_only) throw kbhip::Error(KBHIP_EINVAL, "encode-only session has no device state");
+        kbhip::require_no_tickets(s->s);
+        HIPCHK(hipSetDevice(s->s.device));
+        return kbhip::rank_victim_nodes_abi(s->s, task_id, by_score != 0, victims, first, out_node, out_score,
+                                            out_cands, cap, out_info);
+    })
+}
+
+}  // extern "C"

@@ -455,7 +455,7 @@ struct Framework {
         // evictions are summed per node and applied in one launch (flush_evictions)
         const HPod& p = S.pods[v];
         if (ops_out) {
-            ops_out->push_back(NodeOp{0, p.node, 0, p.req});
+            ops_out->push_back(NodeOp{0, p.node, 0, p.req, S.jobs[p.job].queue});
             on_deallocate(v);
             return;
         }

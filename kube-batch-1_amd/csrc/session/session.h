@@ -10,7 +10,8 @@
 // sweeps, the actions' C-ABI entry points), 06_carry (session carry-over),
 // 07_abi (the remaining C-ABI entry points), 08_walk (the walk read-outs),
 // 09_rank (kbhip_rank_nodes), 10_ops (kbhip_apply_ops), 11_evict (the reclaim /
-// preempt actions and the device ranking of a task's nodes).  framework.h, which
+// preempt actions and the device ranking of a task's nodes), 12_victims (the
+// victim-candidate table and kbhip_rank_victim_nodes).  framework.h, which
 // the parts running actions include, is the C++ mirror of the Go framework they
 // share: the heaps, the ordering plugins, the status index, the statements.
 //
@@ -625,6 +626,20 @@ struct Session {
     vector<int32_t> ops_sim;
     vector<uint8_t> op_mark;
     uint64_t op_mark_gen = ~0ull;
+    // kbhip_rank_victim_nodes (12_victims.cpp): the victim-candidate table [Q + 1][4][npad] (VictArgs,
+    // kbhip_internal.h) on the host and the device.  vict_live: both are current — built by the first ranking
+    // that needs it, kept current by kbhip_apply_ops, cleared by every other call that changes pod statuses
+    // (vict_stale below) and rebuilt by the next ranking.  b_vict_own / h_vict_own: the job's own list of one
+    // call (sums, then nodes); b_vict_blk / b_vict_keys / b_vict_cands: the full path's compaction;
+    // h_vict_out: pinned, [0] = the kept count, then the window's candidate counts.
+    vector<int64_t> vict_tab;
+    bool vict_live = false;
+    DevBuf b_vict, b_vict_own, b_vict_blk, b_vict_keys, b_vict_cands;
+    size_t vict_own_cap = 0;
+    uint8_t* h_vict_own = nullptr;
+    size_t h_vict_own_cap = 0;
+    int32_t* h_vict_out = nullptr;
+    size_t h_vict_out_cap = 0;
     int32_t fallback = -1;  // lowest node index holding a session-placed pod (nodeorder.go:78-93)
     vector<int32_t> sess_cnt;  // per node: session-placed pods on it (fallback after an unpipeline)
     std::unique_ptr<AffinityModel> aff;       // pod (anti-)affinity model (kept for evictions / carry)
@@ -851,6 +866,12 @@ struct Session {
         h_ops = nullptr;
         if (ev_ops) { (void)hipEventDestroy(ev_ops); ev_ops = nullptr; }
         b_ops.release();
+        if (h_vict_own) MemPool::get().give(MemPool::kPinned, h_vict_own, h_vict_own_cap, device);
+        h_vict_own = nullptr;
+        if (h_vict_out) MemPool::get().give(MemPool::kPinned, h_vict_out, h_vict_out_cap, device);
+        h_vict_out = nullptr;
+        for (DevBuf* b : {&b_vict, &b_vict_own, &b_vict_blk, &b_vict_keys, &b_vict_cands}) b->release();
+        vict_live = false;
         h_out = nullptr;
         if (cu_masked) {  // streams of option "cu_split" are this session's own
             for (int k = 1; k <= kMaxDep; ++k)
@@ -1200,7 +1221,19 @@ void first_fit(Session& S, const int32_t* ids, int n, int32_t* out_node);
 struct NodeOp {
     int32_t kind, node, cls;
     R3 req;
+    int32_t queue = -1;  // an eviction: the pod's job's queue (the victim-candidate table's row)
 };
+// kbhip_rank_victim_nodes (12_victims.cpp).  vict_stale: the call that follows changes pod statuses outside
+// kbhip_apply_ops — the victim-candidate table is rebuilt by the next ranking that needs it.
+inline void vict_stale(Session& S) { S.vict_live = false; }
+// A candidate victim: Running with a Running copy on its node, and a job (EvictAction::build_node_tasks' run_copy).
+inline bool vict_candidate(const Session& S, const HPod& p) {
+    return p.status == Running && !p.node_rel && p.job >= 0 && on_node_of(p) && p.node < S.n_total;
+}
+// a batch of kbhip_apply_ops on the host copy of a live table (the device copy: launch_apply_ops)
+void vict_apply_evictions(Session& S, const vector<NodeOp>& ops);
+int64_t rank_victim_nodes_abi(Session& S, int pod, bool by_score, int mode, int64_t first, int32_t* out_node,
+                              int32_t* out_score, int32_t* out_cands, int64_t cap, int64_t* out_info);
 int64_t apply_ops(Session& S, const uint8_t* op, const int32_t* pod, const int32_t* node, int64_t n,
                   int64_t* out_launches);
 

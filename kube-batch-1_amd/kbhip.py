@@ -21,6 +21,7 @@ ALLOCATED, PIPELINED, EVICTED = 1, 2, 3
 EV_DELETE, EV_SUCCEEDED, EV_FAILED = 1, 2, 3  # kbhip_session_carry_events
 STOP_ALL, STOP_UNASSIGNED, STOP_READY = 0, 1, 2
 OP_EVICT, OP_PIPELINE, OP_UNPIPELINE, OP_UNEVICT = 1, 2, 3, 4  # kbhip_apply_ops
+VICTIMS_OTHER_QUEUES, VICTIMS_QUEUE_OTHER_JOBS, VICTIMS_SAME_JOB = 1, 2, 3  # kbhip_rank_victim_nodes
 
 # int kbhip_* entry points declared by include/kbhip.h
 EXPORTS = ("kbhip_device_count", "kbhip_session_open", "kbhip_session_open_file", "kbhip_place_job",
@@ -33,7 +34,7 @@ EXPORTS = ("kbhip_device_count", "kbhip_session_open", "kbhip_session_open_file"
            "kbhip_session_carry_events", "kbhip_shard_connect_mailbox", "kbhip_shard_mailbox_fits", "kbhip_place_job_submit",
            "kbhip_place_job_wait", "kbhip_place_job_cancel", "kbhip_time_sweeps", "kbhip_time_rank_multi",
            "kbhip_session_carry_snapshot", "kbhip_walk_visits", "kbhip_fit_deltas", "kbhip_rank_nodes",
-           "kbhip_apply_ops")
+           "kbhip_apply_ops", "kbhip_rank_victim_nodes")
 
 RED_MAX_U64, RED_MIN_I64, RED_MAX_I64, RED_SUM_I64 = 0, 1, 2, 3
 ALLREDUCE_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint64), ctypes.c_int32,
@@ -135,6 +136,8 @@ def lib() -> ctypes.CDLL:
         L.kbhip_rank_nodes.restype = i64
         L.kbhip_apply_ops.argtypes = [vp, vp, vp, vp, i64, vp]
         L.kbhip_apply_ops.restype = i64
+        L.kbhip_rank_victim_nodes.argtypes = [vp, i32, i32, i32, i64, vp, vp, vp, i64, vp]
+        L.kbhip_rank_victim_nodes.restype = i64
         _lib = L
     return _lib
 
@@ -248,6 +251,36 @@ class Session:
         _check(n if n < 0 else 0)
         k = max(min(n, int(first) + int(cap)) - int(first), 0)
         return n, node[:k].copy(), score[:k].copy()
+
+    def rank_victim_nodes(self, task_id: int, by_score: bool = True, victims: int = VICTIMS_OTHER_QUEUES,
+                          first: int = 0, cap: Optional[int] = None):
+        """kbhip_rank_victim_nodes: rank_nodes' walk without the nodes that can
+        yield no victim set for the task (no candidate of the `victims` kind, or
+        candidates together strictly short of its InitResreq in all three
+        resources): (total, nodes, scores, cands, info).  cands: the candidate
+        count per returned node; info: {"head", "rebuilt", "launches"} of the
+        call that read the entries.  cap=None: a size query, then every entry
+        from `first`."""
+        bs, vi = int(by_score), int(victims)
+        info = np.zeros(3, np.int64)
+        fn = lib().kbhip_rank_victim_nodes
+        rebuilt = 0
+        if cap is None:
+            n = int(fn(self._h, int(task_id), bs, vi, int(first), None, None, None, 0, _p(info)))
+            _check(n if n < 0 else 0)
+            rebuilt = int(info[1])
+            cap = max(n - int(first), 0)
+            if cap == 0:
+                z = np.zeros(0, np.int32)
+                return n, z, z.copy(), z.copy(), {"head": int(info[0]), "rebuilt": rebuilt, "launches": int(info[2])}
+        node = np.full(max(int(cap), 1), -1, np.int32)
+        score = np.zeros(max(int(cap), 1), np.int32)
+        cands = np.zeros(max(int(cap), 1), np.int32)
+        n = int(fn(self._h, int(task_id), bs, vi, int(first), _p(node), _p(score), _p(cands), int(cap), _p(info)))
+        _check(n if n < 0 else 0)
+        k = max(min(n, int(first) + int(cap)) - int(first), 0)
+        return (n, node[:k].copy(), score[:k].copy(), cands[:k].copy(),
+                {"head": int(info[0]), "rebuilt": int(info[1]) | rebuilt, "launches": int(info[2])})
 
     def apply_ops(self, ops, pods, nodes=None) -> int:
         """kbhip_apply_ops: the evictions and pipelines a host-driven reclaim /
