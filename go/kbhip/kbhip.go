@@ -302,6 +302,65 @@ func (e *Engine) RankVictimNodes(task int32, byScore bool, victims int32, first,
 	return int64(t), nodes[:got], scores[:got], cands[:got], info, nil
 }
 
+// RankHeadsMax is the most tasks one RankHeads call answers (KBHIP_RANK_HEADS_MAX).
+const RankHeadsMax = int(C.KBHIP_RANK_HEADS_MAX)
+
+// Head is one task's answer of RankHeads: the walk's length and its first
+// min(cap, Total) entries (Cands all 0 with victims 0).
+type Head struct {
+	Total  int64
+	Nodes  []int32
+	Scores []int32
+	Cands  []int32
+}
+
+// HeadsInfo says how a RankHeads call was served.
+type HeadsInfo struct {
+	Rebuilt  bool  // the call (re)built the candidate table
+	Launches int64 // kernel launches issued: 2, plus one per distinct class with inter-pod priority terms
+	GridX    int64 // the x size of the sweep's grid
+}
+
+// RankHeads answers the walk heads of up to RankHeadsMax Pending tasks in one
+// sweep launch, one merge launch and one copy (kbhip_rank_heads): heads[i] is
+// what RankNodes(tasks[i], byScore, 0, cap) returns with victims 0, and what
+// RankVictimNodes(tasks[i], byScore, victims, 0, cap) returns with one of the
+// Victims* kinds.  1 <= cap <= 64; a task may appear more than once.  The
+// heads describe the session at the call: a host that prefetches them for the
+// tasks its loop will rank next discards what it has not consumed as soon as
+// it sends an ApplyOps.  The session state is not changed.
+func (e *Engine) RankHeads(tasks []int32, byScore bool, victims int32, cap int) (heads []Head, info HeadsInfo, err error) {
+	if len(tasks) == 0 { // &tasks[0] of an empty slice panics
+		return nil, info, nil
+	}
+	if len(tasks) > RankHeadsMax || cap < 1 || cap > 64 {
+		return nil, info, fmt.Errorf("kbhip rank_heads: %d tasks (1..%d), cap %d (1..64)", len(tasks), RankHeadsMax, cap)
+	}
+	n := len(tasks)
+	total := make([]int64, n)
+	nodes := make([]int32, n*cap)
+	scores := make([]int32, n*cap)
+	cands := make([]int32, n*cap)
+	var raw [3]C.int64_t
+	if r := C.kbhip_rank_heads(e.s, (*C.int32_t)(unsafe.Pointer(&tasks[0])), C.int32_t(n), boolI32(byScore),
+		C.int32_t(victims), C.int32_t(cap), (*C.int64_t)(unsafe.Pointer(&total[0])),
+		(*C.int32_t)(unsafe.Pointer(&nodes[0])), (*C.int32_t)(unsafe.Pointer(&scores[0])),
+		(*C.int32_t)(unsafe.Pointer(&cands[0])), &raw[0]); r < 0 {
+		return nil, info, lastErr("rank_heads", C.int(r))
+	}
+	info = HeadsInfo{Rebuilt: raw[0] != 0, Launches: int64(raw[1]), GridX: int64(raw[2])}
+	heads = make([]Head, n)
+	for i := range heads {
+		k := total[i]
+		if k > int64(cap) {
+			k = int64(cap)
+		}
+		lo, hi := i*cap, i*cap+int(k)
+		heads[i] = Head{Total: total[i], Nodes: nodes[lo:hi:hi], Scores: scores[lo:hi:hi], Cands: cands[lo:hi:hi]}
+	}
+	return heads, info, nil
+}
+
 // Op is one decision of a host-kept reclaim / preempt loop for ApplyOps.
 // Node is read for OpPipeline only (an eviction uses the pod's own node).
 type Op struct {

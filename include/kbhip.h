@@ -344,6 +344,45 @@ int64_t kbhip_rank_victim_nodes(kb_session* s, int32_t task_id, int32_t by_score
                                 int32_t* out_node, int32_t* out_score, int32_t* out_cands, int64_t cap,
                                 int64_t* out_info);
 
+/* kbhip_rank_heads <- the walk heads of up to KBHIP_RANK_HEADS_MAX tasks of
+ * the session as it stands, from one sweep launch, one merge launch and one
+ * copy back: a ranking call's fixed cost (upload, launches, copy, wait) paid
+ * once per batch instead of once per task.  A host forms such a batch wherever
+ * its loop ranks task after task with no operation in between: preempt's
+ * within-job phase trying one preemptor per under-request job
+ * (preempt.go:151-181), the tasks of one preemptor job until one is assigned
+ * (preempt.go:101-138), reclaim's queues each finding no node.
+ * For task_ids[i], out_total[i] and row i of the outputs — out_node,
+ * out_score (optional), out_cands (optional), n_tasks rows of cap entries —
+ * are exactly what kbhip_rank_nodes(task, by_score, 0, .., cap) returns and
+ * writes when victims is 0, and what kbhip_rank_victim_nodes(task, by_score,
+ * victims, 0, .., cap, ..) returns and writes when victims is one of
+ * KBHIP_VICTIMS_* (out_cands entries are 0 with victims 0).  The entries of a
+ * row beyond min(cap, total) are -1 (node) and 0 (score, cands): the call
+ * defines its whole output.  1 <= cap <= 64.  A task may appear more than
+ * once; tasks of different classes, jobs and queues, plain classes,
+ * pod-affinity classes and classes with inter-pod priority terms mix freely.
+ * Returns n_tasks (0 for n_tasks == 0, which does nothing).  out_info
+ * (optional, 3 entries) = whether the call (re)built the candidate table, the
+ * kernel launches it issued (2, plus one per distinct class with inter-pod
+ * priority terms when by_score is 1, plus one when pod-affinity count changes
+ * of earlier operations were still to be applied), the x size of the sweep's
+ * grid.  kbhip_stats.rank_heads counts one per answered task.
+ * The heads describe the session at the call: a host that prefetches them
+ * discards what it has not consumed as soon as it sends a kbhip_apply_ops.
+ * The call changes what kbhip_rank_victim_nodes changes — the candidate
+ * table's currency — and nothing else.  The whole batch is validated before
+ * any device work, and a refused call writes nothing.  KBHIP_EINVAL: a null
+ * session, task_ids, out_total or out_node; n_tasks, cap, by_score or victims
+ * out of range; a task without a class or not Pending, with victims != 0 a
+ * task without a job (the message names the index in task_ids); an
+ * encode-only session; submitted pops outstanding.  KBHIP_EUNSUPPORTED: a
+ * node-sharded session, a candidate table above 512 MB. */
+#define KBHIP_RANK_HEADS_MAX 64
+int64_t kbhip_rank_heads(kb_session* s, const int32_t* task_ids, int32_t n_tasks, int32_t by_score,
+                         int32_t victims, int32_t cap, int64_t* out_total, int32_t* out_node,
+                         int32_t* out_score, int32_t* out_cands, int64_t* out_info);
+
 /* Measurement hook (bench.py's sweep roofline): kbhip_sweep_scores' sweep
  * kernel for each given task, launched back to back on the session stream
  * with no copies in between; *out_mean_us = device time per launch (one

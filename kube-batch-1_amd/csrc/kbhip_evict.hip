@@ -773,14 +773,17 @@ __device__ __forceinline__ bool vict_keep(const VictArgs& v, const Vict4& a) {
 // FILT: the lane that evaluates a node also loads the node's candidate sums
 // (before the evaluation: the loads run under it) and zeroes its key when the
 // node fails the test; without FILT v is never read.
+// lists / bcnt: the request's block lists and block counts (block blockIdx.x
+// writes list blockIdx.x); slot: the PopCtrl task slot that holds the
+// request's inter-pod min / max; stride: the nodes one step of the grid
+// covers (gridDim.x * kBlock).  s_top / s_cnt: the block's LDS (the caller's,
+// so that a kernel with two instantiations of the body declares it once).
 template <bool PLAIN, bool FILT>
 __device__ __forceinline__ void rank_head(const Conf& cf, const NodeCols& nc, const DevTables& t, const TaskClass& c,
-                                          const PopCtrl* ctrl, int by_score, uint64_t* lists, uint32_t* bcnt,
-                                          const VictArgs& v) {
-    __shared__ uint64_t s_top[kHeadWaves][64];
-    __shared__ uint32_t s_cnt[kHeadWaves];
+                                          const PopCtrl* ctrl, int by_score, int slot, int stride, uint64_t* lists,
+                                          uint32_t* bcnt, const VictArgs& v, uint64_t (*s_top)[64],
+                                          uint32_t* s_cnt) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int stride = gridDim.x * kBlock;
     uint64_t top = 0;  // lane i: the wave's i-th best key so far
     uint32_t cnt = 0;  // passing nodes of the wave (uniform)
     // b is the wave's first node of the step: uniform, so every lane runs the
@@ -817,7 +820,8 @@ __device__ __forceinline__ void rank_head(const Conf& cf, const NodeCols& nc, co
             if (by_score) {
                 int32_t s = 0;
                 bool passed = false;
-                (void)eval_node_aff(cf, c, t, nc, n, ctrl->ipa_lo[0], ctrl->ipa_hi[0], ctrl->fallback, &s, &passed);
+                (void)eval_node_aff(cf, c, t, nc, n, ctrl->ipa_lo[slot], ctrl->ipa_hi[slot], ctrl->fallback, &s,
+                                    &passed);
                 k = passed ? pack_key(s, n + nc.base, 0) : 0;
             } else {
                 k = eval_first_fit(cf, c, t, nc, n);
@@ -844,17 +848,22 @@ template <bool PLAIN>
 __global__ __launch_bounds__(kBlock) void k_rank_head(Conf cf, NodeCols nc, DevTables t, TaskClass c,
                                                       const PopCtrl* ctrl, int by_score, uint64_t* lists,
                                                       uint32_t* bcnt) {
-    rank_head<PLAIN, false>(cf, nc, t, c, ctrl, by_score, lists, bcnt, VictArgs{});
+    __shared__ uint64_t s_top[kHeadWaves][64];
+    __shared__ uint32_t s_cnt[kHeadWaves];
+    rank_head<PLAIN, false>(cf, nc, t, c, ctrl, by_score, 0, gridDim.x * kBlock, lists, bcnt, VictArgs{}, s_top,
+                            s_cnt);
 }
 template <bool PLAIN>
 __global__ __launch_bounds__(kBlock) void k_rank_head_vict(Conf cf, NodeCols nc, DevTables t, TaskClass c,
                                                            const PopCtrl* ctrl, int by_score, uint64_t* lists,
                                                            uint32_t* bcnt, VictArgs v) {
-    rank_head<PLAIN, true>(cf, nc, t, c, ctrl, by_score, lists, bcnt, v);
+    __shared__ uint64_t s_top[kHeadWaves][64];
+    __shared__ uint32_t s_cnt[kHeadWaves];
+    rank_head<PLAIN, true>(cf, nc, t, c, ctrl, by_score, 0, gridDim.x * kBlock, lists, bcnt, v, s_top, s_cnt);
 }
 
-__global__ __launch_bounds__(kBlock) void k_rank_head_merge(const uint64_t* lists, const uint32_t* bcnt, int nblk,
-                                                            uint64_t* out) {
+__device__ __forceinline__ void rank_head_merge(const uint64_t* lists, const uint32_t* bcnt, int nblk,
+                                                uint64_t* out) {
     __shared__ uint64_t s_top[kHeadWaves][64];
     __shared__ uint32_t s_cnt[kHeadWaves];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -871,6 +880,80 @@ __global__ __launch_bounds__(kBlock) void k_rank_head_merge(const uint64_t* list
         for (int w = 0; w < kHeadWaves; ++w) tot += s_cnt[w];
         out[kTopK] = tot;
     }
+}
+__global__ __launch_bounds__(kBlock) void k_rank_head_merge(const uint64_t* lists, const uint32_t* bcnt, int nblk,
+                                                            uint64_t* out) {
+    rank_head_merge(lists, bcnt, nblk, out);
+}
+
+// ---------------------------------------------------------------------------
+// The heads of several tasks of one session (kbhip_rank_heads): the two
+// kernels above with blockIdx.y as the request.  Request r's descriptor
+// (HeadDesc: its class, its victim test, its PopCtrl slot) is read from device
+// memory; its blocks write lists [r gridDim.x, (r + 1) gridDim.x) of the
+// scratch and k_rank_heads_merge's block r merges those into out[r][0 .. 64].
+// Whether a request's class takes the PLAIN body is uniform per block.
+// ---------------------------------------------------------------------------
+template <bool FILT>
+__global__ __launch_bounds__(kBlock) void k_rank_heads(Conf cf, NodeCols nc, DevTables t, const HeadDesc* d,
+                                                       const PopCtrl* ctrl, int by_score, uint64_t* lists,
+                                                       uint32_t* bcnt) {
+    __shared__ uint64_t s_top[kHeadWaves][64];
+    __shared__ uint32_t s_cnt[kHeadWaves];
+    const HeadDesc& q = d[blockIdx.y];
+    const size_t r = (size_t)blockIdx.y * gridDim.x;
+    const int stride = gridDim.x * kBlock;
+    if (by_score && !q.c.aff && q.c.ipa_n == 0)
+        rank_head<true, FILT>(cf, nc, t, q.c, ctrl, by_score, q.slot, stride, lists + r * 64, bcnt + r, q.v, s_top,
+                              s_cnt);
+    else
+        rank_head<false, FILT>(cf, nc, t, q.c, ctrl, by_score, q.slot, stride, lists + r * 64, bcnt + r, q.v, s_top,
+                               s_cnt);
+}
+__global__ __launch_bounds__(kBlock) void k_rank_heads_merge(const uint64_t* lists, const uint32_t* bcnt, int nblk,
+                                                             uint64_t* out) {
+    const size_t r = (size_t)blockIdx.x * nblk;
+    rank_head_merge(lists + r * 64, bcnt + r, nblk, out + (size_t)blockIdx.x * (kTopK + 1));
+}
+
+// The sweep's grid x for n_req requests.  A request alone takes the
+// single-task grid (rank_head_blocks: one block per CU at most).  More
+// requests share kHeadsPerCU blocks per CU — what is resident at once at the
+// kernel's register count, so the whole grid is one wave of blocks — each
+// request getting an equal part of them, at least one block.
+constexpr int kHeadsPerCU = 4;
+constexpr int kHeadsMaxLists = kHeadsPerCU * kHeadMaxBlocks;  // >= n_req * rank_heads_bx(n, n_req)
+int rank_heads_bx(int n_nodes, int n_req) {
+    const int one = rank_head_blocks(n_nodes);
+    const int cus = cu_count() < kHeadMaxBlocks ? cu_count() : kHeadMaxBlocks;
+    const int part = n_req > 0 ? kHeadsPerCU * cus / n_req : one;
+    return part < 1 ? 1 : part < one ? part : one;
+}
+// scratch, in 8-byte words: kMaxChunk results (kTopK keys + the count each), the block lists, the block counts
+size_t rank_heads_words() {
+    return (size_t)kMaxChunk * (kTopK + 1) + (size_t)kHeadsMaxLists * 64 + kHeadsMaxLists / 2;
+}
+
+hipError_t launch_rank_heads(const Conf& cf, const NodeCols& nc, const DevTables& t, const HeadDesc* d_desc, int n_req,
+                             bool filt, const PopCtrl* ctrl, int by_score, uint64_t* scratch, int* bx_out,
+                             hipStream_t st) {
+    static_assert(kMaxChunk <= kHeadsMaxLists, "one list per request at least");
+    if (n_req < 1 || n_req > kMaxChunk) return hipErrorInvalidValue;
+    uint64_t* out = scratch;
+    uint64_t* lists = scratch + (size_t)kMaxChunk * (kTopK + 1);
+    uint32_t* bcnt = reinterpret_cast<uint32_t*>(lists + (size_t)kHeadsMaxLists * 64);
+    const int bx = rank_heads_bx(nc.n, n_req);
+    if ((size_t)bx * n_req > (size_t)kHeadsMaxLists) return hipErrorInvalidValue;
+    if (filt)
+        hipLaunchKernelGGL((k_rank_heads<true>), dim3(bx, n_req), dim3(kBlock), 0, st, cf, nc, t, d_desc, ctrl,
+                           by_score, lists, bcnt);
+    else
+        hipLaunchKernelGGL((k_rank_heads<false>), dim3(bx, n_req), dim3(kBlock), 0, st, cf, nc, t, d_desc, ctrl,
+                           by_score, lists, bcnt);
+    hipLaunchKernelGGL(k_rank_heads_merge, dim3(n_req), dim3(kBlock), 0, st, (const uint64_t*)lists,
+                       (const uint32_t*)bcnt, bx, out);
+    if (bx_out) *bx_out = bx;
+    return hipGetLastError();
 }
 
 int rank_head_blocks(int n_nodes) {

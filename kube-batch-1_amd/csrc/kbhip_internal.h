@@ -123,6 +123,26 @@ struct VictArgs {
 hipError_t launch_rank_head_vict(const Conf& cf, const NodeCols& nc, const DevTables& t, const TaskClass& c,
                                  const PopCtrl* ctrl, int by_score, const VictArgs& v, uint64_t* scratch,
                                  hipStream_t st);
+// kbhip_rank_heads: the heads of n_req (1 .. kMaxChunk) tasks of one session in
+// one sweep launch (grid (bx, n_req), blockIdx.y = the request) and one merge
+// launch (grid n_req).  Request r is d_desc[r] in device memory: its class,
+// its victim test (read with filt only; own_node / own_sum point into the
+// call's concatenated own-job lists) and the PopCtrl task slot that holds its
+// inter-pod min / max (launch_ipa_minmax(…, slot, …) before the sweep; several
+// requests of one class share a slot).  Afterwards scratch[r (kTopK + 1) ..]
+// is request r's result as launch_rank_head leaves one; scratch holds
+// rank_heads_words() 8-byte words whatever the batch.  rank_heads_bx: the
+// sweep's grid x for that many requests.
+struct HeadDesc {
+    TaskClass c;
+    VictArgs v;
+    int32_t slot, pad;
+};
+int rank_heads_bx(int n_nodes, int n_req);
+size_t rank_heads_words();
+hipError_t launch_rank_heads(const Conf& cf, const NodeCols& nc, const DevTables& t, const HeadDesc* d_desc, int n_req,
+                             bool filt, const PopCtrl* ctrl, int by_score, uint64_t* scratch, int* bx_out,
+                             hipStream_t st);
 // The filtered full walk: a stable compaction of launch_rank_sorted's /
 // launch_rank_radix's output (sorted, *count keys) in three launches — per
 // block of kBlock keys the survivors' count (blk[b]), k_rank_scan over blk

@@ -58,6 +58,14 @@ void vict_build(Session& S) {
     S.vict_live = true;
 }
 
+}  // namespace
+
+bool vict_ensure(Session& S) {
+    if (S.vict_live) return false;
+    vict_build(S);
+    return true;
+}
+
 // The candidate tasks of job jb per node: distinct nodes ascending, four sums each.
 void vict_own_list(const Session& S, int jb, vector<int32_t>& node, vector<int64_t>& sum) {
     node.clear();
@@ -91,8 +99,6 @@ int64_t vict_count_host(const Session& S, int mode, int q, const vector<int32_t>
     return S.vict_tab[(size_t)q * 4 * np + n] - own;
 }
 
-}  // namespace
-
 void vict_apply_evictions(Session& S, const vector<NodeOp>& ops) {
     const size_t np = (size_t)S.nc.npad, Q = S.queues.size();
     for (const NodeOp& o : ops) {
@@ -124,8 +130,7 @@ int64_t rank_victim_nodes_abi(Session& S, int pod, bool by_score, int mode, int6
     if (S.world != 1) throw Error(KBHIP_EUNSUPPORTED, "kbhip_rank_victim_nodes on a node-sharded session");
     ov_quiesce(S);
     const int cls = S.pods[pod].cls, N = S.nc.n;
-    const bool rebuilt = !S.vict_live;
-    if (rebuilt) vict_build(S);
+    const bool rebuilt = vict_ensure(S);
     vector<int32_t> own_node;
     vector<int64_t> own_sum;
     if (mode != KBHIP_VICTIMS_OTHER_QUEUES) vict_own_list(S, jb, own_node, own_sum);

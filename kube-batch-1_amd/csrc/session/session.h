@@ -640,6 +640,16 @@ struct Session {
     size_t h_vict_own_cap = 0;
     int32_t* h_vict_out = nullptr;
     size_t h_vict_out_cap = 0;
+    // kbhip_rank_heads (13_heads.cpp).  h_heads_in (pinned) / b_heads_in: one call's upload — a PopCtrl image
+    // of the call's own (slot i: request i's class, inter-pod min / max zero), its HeadDescs, the own-job
+    // lists of its jobs; b_heads: the kernels' scratch (rank_heads_words); h_heads_out (pinned): kMaxChunk
+    // results of kTopK keys and the count.
+    DevBuf b_heads_in, b_heads;
+    size_t heads_in_cap = 0;
+    uint8_t* h_heads_in = nullptr;
+    size_t h_heads_in_cap = 0;
+    uint64_t* h_heads_out = nullptr;
+    size_t h_heads_out_cap = 0;
     int32_t fallback = -1;  // lowest node index holding a session-placed pod (nodeorder.go:78-93)
     vector<int32_t> sess_cnt;  // per node: session-placed pods on it (fallback after an unpipeline)
     std::unique_ptr<AffinityModel> aff;       // pod (anti-)affinity model (kept for evictions / carry)
@@ -872,6 +882,13 @@ struct Session {
         h_vict_out = nullptr;
         for (DevBuf* b : {&b_vict, &b_vict_own, &b_vict_blk, &b_vict_keys, &b_vict_cands}) b->release();
         vict_live = false;
+        if (h_heads_in) MemPool::get().give(MemPool::kPinned, h_heads_in, h_heads_in_cap, device);
+        h_heads_in = nullptr;
+        if (h_heads_out) MemPool::get().give(MemPool::kPinned, h_heads_out, h_heads_out_cap, device);
+        h_heads_out = nullptr;
+        b_heads_in.release();
+        b_heads.release();
+        heads_in_cap = 0;
         h_out = nullptr;
         if (cu_masked) {  // streams of option "cu_split" are this session's own
             for (int k = 1; k <= kMaxDep; ++k)
@@ -1234,6 +1251,16 @@ inline bool vict_candidate(const Session& S, const HPod& p) {
 void vict_apply_evictions(Session& S, const vector<NodeOp>& ops);
 int64_t rank_victim_nodes_abi(Session& S, int pod, bool by_score, int mode, int64_t first, int32_t* out_node,
                               int32_t* out_score, int32_t* out_cands, int64_t cap, int64_t* out_info);
+// The parts of that call kbhip_rank_heads (13_heads.cpp) shares.  vict_ensure: the table built unless it is
+// live (true: built now).  vict_own_list: job jb's candidates per node, distinct nodes ascending with four
+// sums each.  vict_count_host: vict_cand's count of node n on the host copy of the table.
+bool vict_ensure(Session& S);
+void vict_own_list(const Session& S, int jb, vector<int32_t>& node, vector<int64_t>& sum);
+int64_t vict_count_host(const Session& S, int mode, int q, const vector<int32_t>& own_node,
+                        const vector<int64_t>& own_sum, int n);
+int64_t rank_heads_abi(Session& S, const int32_t* task_ids, int n_tasks, bool by_score, int mode, int cap,
+                       int64_t* out_total, int32_t* out_node, int32_t* out_score, int32_t* out_cands,
+                       int64_t* out_info);
 int64_t apply_ops(Session& S, const uint8_t* op, const int32_t* pod, const int32_t* node, int64_t n,
                   int64_t* out_launches);
 

@@ -22,6 +22,7 @@ EV_DELETE, EV_SUCCEEDED, EV_FAILED = 1, 2, 3  # kbhip_session_carry_events
 STOP_ALL, STOP_UNASSIGNED, STOP_READY = 0, 1, 2
 OP_EVICT, OP_PIPELINE, OP_UNPIPELINE, OP_UNEVICT = 1, 2, 3, 4  # kbhip_apply_ops
 VICTIMS_OTHER_QUEUES, VICTIMS_QUEUE_OTHER_JOBS, VICTIMS_SAME_JOB = 1, 2, 3  # kbhip_rank_victim_nodes
+RANK_HEADS_MAX = 64  # KBHIP_RANK_HEADS_MAX: tasks per kbhip_rank_heads
 
 # int kbhip_* entry points declared by include/kbhip.h
 EXPORTS = ("kbhip_device_count", "kbhip_session_open", "kbhip_session_open_file", "kbhip_place_job",
@@ -34,7 +35,7 @@ EXPORTS = ("kbhip_device_count", "kbhip_session_open", "kbhip_session_open_file"
            "kbhip_session_carry_events", "kbhip_shard_connect_mailbox", "kbhip_shard_mailbox_fits", "kbhip_place_job_submit",
            "kbhip_place_job_wait", "kbhip_place_job_cancel", "kbhip_time_sweeps", "kbhip_time_rank_multi",
            "kbhip_session_carry_snapshot", "kbhip_walk_visits", "kbhip_fit_deltas", "kbhip_rank_nodes",
-           "kbhip_apply_ops", "kbhip_rank_victim_nodes")
+           "kbhip_apply_ops", "kbhip_rank_victim_nodes", "kbhip_rank_heads")
 
 RED_MAX_U64, RED_MIN_I64, RED_MAX_I64, RED_SUM_I64 = 0, 1, 2, 3
 ALLREDUCE_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint64), ctypes.c_int32,
@@ -138,6 +139,8 @@ def lib() -> ctypes.CDLL:
         L.kbhip_apply_ops.restype = i64
         L.kbhip_rank_victim_nodes.argtypes = [vp, i32, i32, i32, i64, vp, vp, vp, i64, vp]
         L.kbhip_rank_victim_nodes.restype = i64
+        L.kbhip_rank_heads.argtypes = [vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp]
+        L.kbhip_rank_heads.restype = i64
         _lib = L
     return _lib
 
@@ -281,6 +284,30 @@ class Session:
         k = max(min(n, int(first) + int(cap)) - int(first), 0)
         return (n, node[:k].copy(), score[:k].copy(), cands[:k].copy(),
                 {"head": int(info[0]), "rebuilt": int(info[1]) | rebuilt, "launches": int(info[2])})
+
+    def rank_heads(self, task_ids, by_score: bool = True, victims: int = 0, cap: int = 64):
+        """kbhip_rank_heads: the walk heads of up to RANK_HEADS_MAX pending
+        tasks of the session as it stands, from one sweep launch, one merge
+        launch and one copy: (totals[n], nodes[n, cap], scores[n, cap],
+        cands[n, cap], info).  Row i is what rank_nodes(task_ids[i], by_score,
+        0, cap) answers (victims=0) or rank_victim_nodes(task_ids[i], by_score,
+        victims, 0, cap) (victims 1..3), padded beyond the total with node -1,
+        score 0, cands 0.  info (3 int64): table rebuilt, kernel launches, the
+        sweep grid's x size."""
+        ids = np.ascontiguousarray(task_ids, dtype=np.int32).reshape(-1)
+        n, cap = int(ids.size), int(cap)
+        rows = max(n, 1) * max(cap, 1)
+        total = np.zeros(max(n, 1), np.int64)
+        node = np.full(rows, -1, np.int32)
+        score = np.zeros(rows, np.int32)
+        cands = np.zeros(rows, np.int32)
+        info = np.zeros(3, np.int64)
+        r = int(lib().kbhip_rank_heads(self._h, _p(ids), n, int(by_score), int(victims), cap, _p(total), _p(node),
+                                       _p(score), _p(cands), _p(info)))
+        _check(r if r < 0 else 0)
+        shape = (n, max(cap, 0))
+        return (total[:n].copy(), node[: n * cap].reshape(shape), score[: n * cap].reshape(shape),
+                cands[: n * cap].reshape(shape), info)
 
     def apply_ops(self, ops, pods, nodes=None) -> int:
         """kbhip_apply_ops: the evictions and pipelines a host-driven reclaim /
