@@ -490,11 +490,12 @@ hipError_t launch_rank_radix(const uint64_t* keys, int n, const uint32_t* count,
                              uint64_t* sorted, hipStream_t st) {
     const int nblk = (n + kBlock - 1) / kBlock;
     if (nblk < 1) return hipSuccess;
-    // pass 0: keys -> sorted, 1: sorted -> tmp, 2: tmp -> sorted, 3: sorted -> tmp ... ending in sorted
+    // pass 0: keys -> tmp, 1: tmp -> sorted, 2: sorted -> tmp, 3: tmp -> sorted: the fourth pass (the
+    // score's top byte, where negative and non-negative scores part) ends in sorted
     const uint64_t* in = keys;
     uint64_t* bufs[2] = {tmp, sorted};
     for (int p = 0; p < 4; ++p) {
-        uint64_t* out = bufs[(p + 1) & 1];
+        uint64_t* out = bufs[p & 1];
         const uint32_t* cnt = p == 0 ? nullptr : count;  // pass 0 drops the failing nodes' zero keys
         hipLaunchKernelGGL(k_radix_bucket, dim3(nblk), dim3(kBlock), 0, st, in, n, cnt, 8 * p, hist, nblk);
         hipLaunchKernelGGL(k_rank_scan, dim3(1), dim3(1024), 0, st, hist, 256 * nblk);
