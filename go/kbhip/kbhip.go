@@ -361,6 +361,84 @@ func (e *Engine) RankHeads(tasks []int32, byScore bool, victims int32, cap int) 
 	return heads, info, nil
 }
 
+// The verdict codes of ExplainTasks (KBHIP_WHY_*): the low four bits of a
+// verdict byte; the WhyShort* bits accompany the codes 0..2.
+const (
+	WhyFitsIdle      = uint8(C.KBHIP_WHY_FITS_IDLE)
+	WhyFitsReleasing = uint8(C.KBHIP_WHY_FITS_RELEASING)
+	WhyResources     = uint8(C.KBHIP_WHY_RESOURCES)
+	WhyPodCount      = uint8(C.KBHIP_WHY_POD_COUNT)
+	WhyNodeSelector  = uint8(C.KBHIP_WHY_NODE_SELECTOR)
+	WhyHostPorts     = uint8(C.KBHIP_WHY_HOST_PORTS)
+	WhyUnschedulable = uint8(C.KBHIP_WHY_UNSCHEDULABLE)
+	WhyTaints        = uint8(C.KBHIP_WHY_TAINTS)
+	WhyPodAffinity   = uint8(C.KBHIP_WHY_POD_AFFINITY)
+	WhyScoreError    = uint8(C.KBHIP_WHY_SCORE_ERROR)
+	WhyShortCPU      = uint8(C.KBHIP_WHY_SHORT_CPU)
+	WhyShortMem      = uint8(C.KBHIP_WHY_SHORT_MEM)
+	WhyShortGPU      = uint8(C.KBHIP_WHY_SHORT_GPU)
+)
+
+// ExplainMax is the most tasks one ExplainTasks call answers, ExplainBins the
+// length of a task's histogram.
+const (
+	ExplainMax  = int(C.KBHIP_EXPLAIN_MAX)
+	ExplainBins = int(C.KBHIP_EXPLAIN_BINS)
+)
+
+// Explanation is one task's answer of ExplainTasks.  Hist[c], c in 0..9, counts
+// the nodes with code c; Hist[11..13] the nodes of the walk short of cpu /
+// memory / GPU; Hist[14] the walk; Hist[15] the nodes.  Verdict (nil unless
+// asked for) holds one byte per node.
+type Explanation struct {
+	Hist    [16]int64
+	Verdict []uint8
+}
+
+// ExplainInfo says how an ExplainTasks call was served.
+type ExplainInfo struct {
+	Launches int64 // kernel launches issued: 2, plus one when pod-affinity count changes were still to be applied
+	GridX    int64 // the x size of the sweep's grid
+	Rows     bool  // per-node verdicts were written
+}
+
+// ExplainTasks answers, for up to ExplainMax Pending tasks of the session as it
+// stands, why each node is or is not in the task's allocate walk
+// (kbhip_explain_tasks): the first step of predicates.go:123-203 that rejects
+// the node, a NodeOrderFn error, or how the node fits.  nNodes is the session's
+// node count; verdicts false skips the per-node bytes (the histograms are the
+// same).  The session state is not changed.
+func (e *Engine) ExplainTasks(tasks []int32, verdicts bool, nNodes int) (out []Explanation, info ExplainInfo, err error) {
+	if len(tasks) == 0 { // &tasks[0] of an empty slice panics
+		return nil, info, nil
+	}
+	if len(tasks) > ExplainMax || nNodes < 0 {
+		return nil, info, fmt.Errorf("kbhip explain_tasks: %d tasks (1..%d), %d nodes", len(tasks), ExplainMax, nNodes)
+	}
+	n := len(tasks)
+	hist := make([]int64, n*ExplainBins)
+	var rows []uint8
+	var rowsPtr *C.uint8_t
+	if verdicts && nNodes > 0 {
+		rows = make([]uint8, n*nNodes)
+		rowsPtr = (*C.uint8_t)(unsafe.Pointer(&rows[0]))
+	}
+	var raw [3]C.int64_t
+	if r := C.kbhip_explain_tasks(e.s, (*C.int32_t)(unsafe.Pointer(&tasks[0])), C.int32_t(n), rowsPtr,
+		(*C.int64_t)(unsafe.Pointer(&hist[0])), &raw[0]); r < 0 {
+		return nil, info, lastErr("explain_tasks", C.int(r))
+	}
+	info = ExplainInfo{Launches: int64(raw[0]), GridX: int64(raw[1]), Rows: raw[2] != 0}
+	out = make([]Explanation, n)
+	for i := range out {
+		copy(out[i].Hist[:], hist[i*ExplainBins:(i+1)*ExplainBins])
+		if rows != nil {
+			out[i].Verdict = rows[i*nNodes : (i+1)*nNodes : (i+1)*nNodes]
+		}
+	}
+	return out, info, nil
+}
+
 // Op is one decision of a host-kept reclaim / preempt loop for ApplyOps.
 // Node is read for OpPipeline only (an eviction uses the pod's own node).
 type Op struct {

@@ -383,6 +383,65 @@ int64_t kbhip_rank_heads(kb_session* s, const int32_t* task_ids, int32_t n_tasks
                          int32_t victims, int32_t cap, int64_t* out_total, int32_t* out_node,
                          int32_t* out_score, int32_t* out_cands, int64_t* out_info);
 
+/* kbhip_explain_tasks <- why each node is, or is not, a node of the allocate
+ * walk of up to KBHIP_EXPLAIN_MAX pending tasks, on the session as it stands:
+ * what the reference logs node by node (allocate.go:128-137, the error
+ * ssn.PredicateFn returned) and what its loop then decides.  For task_ids[i]
+ * and node n the verdict byte out_verdict[i * n_nodes + n] is the code of the
+ * first step that rejects the node, in the reference's order
+ * (predicates.go:123-203, then allocate.go:139-146): a node that is
+ * unschedulable, tainted and full is KBHIP_WHY_POD_COUNT.  A node no step
+ * rejects is in the walk and gets KBHIP_WHY_FITS_IDLE (allocate.go:153 holds:
+ * it would be Allocated), KBHIP_WHY_FITS_RELEASING (only allocate.go:173
+ * holds: Pipelined) or KBHIP_WHY_RESOURCES (neither), or-ed with the
+ * KBHIP_WHY_SHORT_* bits of the resources in which Idle.FitDelta(Resreq) is
+ * negative (resource_info.go:134-147; Idle taken as Idle + Backfilled, as
+ * kbhip_fit_deltas takes it).  With the predicates plugin off the codes 3..8
+ * never occur.  A node's code is in 0..2 exactly where kbhip_sweep_scores
+ * gives it a non-zero key.
+ * out_hist[i * KBHIP_EXPLAIN_BINS + c], c in 0..9 = the nodes with code c;
+ * [10] = 0; [11..13] = the nodes in the walk with the cpu / memory / GPU
+ * short bit; [14] = the nodes in the walk; [15] = the node count.  For a task
+ * that finds no node ([0] == [1] == 0), [14] and [11..13] are the numbers of
+ * JobInfo.FitError (job_info.go:343-372) and [3..9] the reasons of every node
+ * that message leaves out.  The library renders no message: the host formats
+ * them from these counts.
+ * out_verdict is optional (null: no per-node byte is written anywhere, the
+ * histogram is the same).  out_info (optional, 3 entries) = the kernel
+ * launches issued (2, plus one when pod-affinity count changes of earlier
+ * kbhip_apply_ops were still to be applied — they are applied first), the x
+ * size of the sweep's grid, whether verdict rows were written.  A task may
+ * appear more than once; classes of every kind mix freely.
+ * The call is read-only: no node row, no kbhip_walk_visits counter changes,
+ * and a task kbhip_fit_deltas would answer for stays answerable.  The whole
+ * batch is validated before any device work, and a refused call writes
+ * nothing.  Returns n_tasks (0 for n_tasks == 0, which does nothing).
+ * KBHIP_EINVAL: a null session, null task_ids or out_hist with n_tasks > 0;
+ * n_tasks outside 0 .. KBHIP_EXPLAIN_MAX; a task without a class or not
+ * Pending (the message names the index in task_ids); an encode-only session;
+ * submitted pops outstanding.  KBHIP_EUNSUPPORTED: a node-sharded session.
+ * Option "explain_blocks" = k (tests; 0 = automatic) caps the sweep's grid x. */
+#define KBHIP_WHY_FITS_IDLE      0  /* in the walk; allocate.go:153 holds -> would be Allocated */
+#define KBHIP_WHY_FITS_RELEASING 1  /* in the walk; only allocate.go:173 holds -> would be Pipelined */
+#define KBHIP_WHY_RESOURCES      2  /* in the walk; neither fit holds (allocate.go:164-170) */
+#define KBHIP_WHY_POD_COUNT      3  /* predicates.go:127 */
+#define KBHIP_WHY_NODE_SELECTOR  4  /* predicates.go:132-143: nodeSelector or required node affinity */
+#define KBHIP_WHY_HOST_PORTS     5  /* predicates.go:146-157 */
+#define KBHIP_WHY_UNSCHEDULABLE  6  /* predicates.go:160-171 */
+#define KBHIP_WHY_TAINTS         7  /* predicates.go:174-185 */
+#define KBHIP_WHY_POD_AFFINITY   8  /* predicates.go:188-200, including the task's own invalid selector
+                                       (TaskClass::pred_err: the error is returned at this step) */
+#define KBHIP_WHY_SCORE_ERROR    9  /* predicates pass, NodeOrderFn errors (allocate.go:140-145, score_err) */
+#define KBHIP_WHY_SHORT_CPU 0x10    /* codes 0..2 only: FitDelta(Resreq) negative in cpu / memory / GPU, */
+#define KBHIP_WHY_SHORT_MEM 0x20    /* exactly fit_bits' bits 1..3 (resource_info.go:134-147,            */
+#define KBHIP_WHY_SHORT_GPU 0x40    /* Idle taken as Idle + Backfilled, as kbhip_fit_deltas takes it)     */
+#define KBHIP_EXPLAIN_MAX 64
+#define KBHIP_EXPLAIN_BINS 16
+int64_t kbhip_explain_tasks(kb_session* s, const int32_t* task_ids, int32_t n_tasks,
+                            uint8_t* out_verdict /* optional, n_tasks rows of n_nodes */,
+                            int64_t* out_hist   /* n_tasks rows of KBHIP_EXPLAIN_BINS */,
+                            int64_t* out_info   /* optional, 3 */);
+
 /* Measurement hook (bench.py's sweep roofline): kbhip_sweep_scores' sweep
  * kernel for each given task, launched back to back on the session stream
  * with no copies in between; *out_mean_us = device time per launch (one
@@ -696,6 +755,12 @@ int64_t kbhip_debug_table(kb_session* s, const char* name, void* out, int64_t ca
  * it from the CPU oracle and compare the keys with the oracle's). */
 int kbhip_debug_replay(kb_session* s, int32_t n_steps, const int32_t* pods, const int32_t* modes,
                        const int32_t* nodes, const uint8_t* kinds, uint64_t* out_keys);
+/* Test support: kbhip_explain_tasks for one task on an encode-only session's
+ * host tables, by the function the kernel runs (node_verdict, kbhip_eval.h):
+ * out_verdict (optional, n_nodes bytes) and out_hist (KBHIP_EXPLAIN_BINS) as
+ * that call defines them.  KBHIP_EINVAL: a null session or out_hist, a session
+ * with a device, a task without a class. */
+int kbhip_debug_explain(kb_session* s, int32_t task_id, uint8_t* out_verdict, int64_t* out_hist);
 
 const char* kbhip_last_error(void);
 

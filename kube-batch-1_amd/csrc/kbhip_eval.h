@@ -178,6 +178,16 @@ KBHIP_HD int32_t node_score(const Conf& cf, const TaskClass& c, const Row& r, in
     return ((int32_t)lr * cf.w_lr + (int32_t)bra * cf.w_bra + na * cf.w_na + ipa * cf.w_pa) * cf.score_mult;
 }
 
+// allocate.go:153 (InitResreq <= Idle + Backfilled) and :173 (<= Releasing),
+// Resource.LessEqual's epsilon form (resource_info.go:164-168).
+KBHIP_HD bool fit_idle(const TaskClass& c, const Row& r) {
+    return c.ireq_cpu - (r.idle_cpu + r.bf_cpu) < kMinCPU && c.ireq_mem - (r.idle_mem + r.bf_mem) < kMinMem &&
+           c.ireq_gpu - (r.idle_gpu + r.bf_gpu) < kMinGPU;
+}
+KBHIP_HD bool fit_releasing(const TaskClass& c, const Row& r) {
+    return c.ireq_cpu - r.rel_cpu < kMinCPU && c.ireq_mem - r.rel_mem < kMinMem && c.ireq_gpu - r.rel_gpu < kMinGPU;
+}
+
 // Dynamic predicates (pod count, host ports) + fit + key, given the row.
 // passed: predicate pass and score computed (the node is in the walk).
 KBHIP_HD uint64_t dyn_key(const Conf& cf, const TaskClass& c, const DevTables& t,
@@ -196,12 +206,7 @@ KBHIP_HD uint64_t dyn_key(const Conf& cf, const TaskClass& c, const DevTables& t
     if (!ok) return 0;
     const int32_t s = node_score(cf, c, r, na, ipa);
     *score_out = s;
-    // allocate.go:153 (InitResreq <= Idle + Backfilled) and :173 (<= Releasing)
-    const bool fit_acc = c.ireq_cpu - (r.idle_cpu + r.bf_cpu) < kMinCPU &&
-                         c.ireq_mem - (r.idle_mem + r.bf_mem) < kMinMem &&
-                         c.ireq_gpu - (r.idle_gpu + r.bf_gpu) < kMinGPU;
-    const bool fit_rel = c.ireq_cpu - r.rel_cpu < kMinCPU && c.ireq_mem - r.rel_mem < kMinMem &&
-                         c.ireq_gpu - r.rel_gpu < kMinGPU;
+    const bool fit_acc = fit_idle(c, r), fit_rel = fit_releasing(c, r);
     if (!fit_acc && !fit_rel) return 0;
     return pack_key(s, n + nc.base, fit_acc ? 0 : 1);
 }
@@ -329,6 +334,75 @@ KBHIP_HD uint64_t eval_node_aff(const Conf& cf, const TaskClass& c, const DevTab
     const uint64_t k = dyn_key(cf, c, t, nc, r, pw, n, st, na, score_out, passed, ipa);
     if (fit) *fit = fit_bits(c, r, *passed);
     return k;
+}
+
+// Why node n is, or is not, a node of the task's allocate walk
+// (kbhip_explain_tasks; the KBHIP_WHY_* codes of include/kbhip.h): the first
+// step that rejects it in the reference's order — predicates.go:123-203 (pod
+// count, node selector / required node affinity, host ports, unschedulable,
+// taints, pod (anti-)affinity), then NodeOrderFn's error (allocate.go:140-145)
+// — which is not the order static_pred_f and dyn_key test in: they only need
+// the conjunction.  A node no step rejects is in the walk: 0 where allocate.go:153
+// holds, 1 where only :173 does, 2 where neither, with fit_bits' cpu / memory /
+// GPU bits in bits 4..6.  Flags, row, port words and the taint test are loaded
+// before the steps' early exits, as in eval_node.  No score is needed, hence no
+// inter-pod prepass for any class.
+constexpr int kWhyFitsIdle = 0, kWhyFitsReleasing = 1, kWhyResources = 2, kWhyPodCount = 3, kWhyNodeSelector = 4,
+              kWhyHostPorts = 5, kWhyUnschedulable = 6, kWhyTaints = 7, kWhyPodAffinity = 8, kWhyScoreError = 9;
+constexpr int kWhyCodes = 10, kWhyShortShift = 3;  // fit_bits' bits 1..3 << 3 = 0x10, 0x20, 0x40
+constexpr int kWhyBins = 16;  // the histogram of a request (kbhip.h): 10 codes, a gap, 3 short bits, walk, nodes
+struct VerdictIn {  // what node_verdict reads of a node whatever its steps decide (the sweep prefetches it)
+    Row r;          // (the steps use the fit columns, pods and maxtasks: the other loads are dropped)
+    uint64_t pw[4];
+    uint8_t fl;
+};
+KBHIP_HD VerdictIn verdict_in(const TaskClass& c, const NodeCols& nc, int n) {
+    VerdictIn v;
+    v.fl = nc.flags[n];
+    v.r = load_row(nc, n);
+    for (int w = 0; w < 4; ++w) v.pw[w] = 0;
+    if (c.has_ports)
+        for (int w = 0; w < 4; ++w) if (w < port_win(c, nc)) v.pw[w] = nc.ports[port_at(c, nc, w, n)];
+    return v;
+}
+KBHIP_HD uint8_t node_verdict_of(const Conf& cf, const TaskClass& c, const DevTables& t, const NodeCols& nc, int n,
+                                 const VerdictIn& in) {
+    const uint8_t fl = in.fl;
+    const Row& r = in.r;
+    bool port_hit = false, taint_hit = false;
+    if (c.has_ports)                                                     // host_ports.go:96-125
+        for (int w = 0; w < 4; ++w) if (w < port_win(c, nc))
+            if (in.pw[w] & t.masks[c.pconf_off + w]) port_hit = true;
+    for (int w = 0; w < nc.taint_words; ++w)                             // helper/helpers.go:425-440
+        if (nc.taints[(int64_t)w * nc.npad + n] & ~t.masks[c.tol_off + w]) taint_hit = true;
+    if (cf.pred_on) {
+        if (r.maxtasks <= r.pods) return kWhyPodCount;                   // predicates.go:127
+        if (c.nsel_term >= 0 && !term_match(t, nc, t.terms[c.nsel_term], n)) return kWhyNodeSelector;
+        if (c.req_term_n >= 0) {                                         // predicates.go:132-143
+            bool any = false;
+            for (int i = 0; i < c.req_term_n; ++i) any = any || term_match(t, nc, t.terms[c.req_term_off + i], n);
+            if (!any) return kWhyNodeSelector;
+        }
+        if (port_hit) return kWhyHostPorts;                              // predicates.go:146-157
+        if (fl & 1) return kWhyUnschedulable;                            // predicates.go:160-171
+        if (taint_hit) return kWhyTaints;                                // predicates.go:174-185
+        if (c.pred_err || (c.aff && !aff_pred(c, t, nc, n))) return kWhyPodAffinity;  // predicates.go:188-200
+    }
+    if (c.score_err) return kWhyScoreError;                              // allocate.go:140-145
+    const int code = fit_idle(c, r) ? kWhyFitsIdle : fit_releasing(c, r) ? kWhyFitsReleasing : kWhyResources;
+    return (uint8_t)(code | ((fit_bits(c, r, true) & 0xeu) << kWhyShortShift));
+}
+KBHIP_HD uint8_t node_verdict(const Conf& cf, const TaskClass& c, const DevTables& t, const NodeCols& nc, int n) {
+    return node_verdict_of(cf, c, t, nc, n, verdict_in(c, nc, n));
+}
+// A verdict's bins of the request's histogram, as bits: its code's bin, and for
+// a node of the walk bin 14 and the bins 11..13 of its short bits.  Bin 15 (the
+// node count) is every node's.
+KBHIP_HD uint32_t verdict_bins(uint8_t v) {
+    const uint32_t code = v & 15u;
+    uint32_t b = (1u << code) | (1u << 15);
+    if (code <= (uint32_t)kWhyResources) b |= (1u << 14) | ((uint32_t)(v >> 4) & 7u) << 11;
+    return b;
 }
 
 // Backfill's node test (backfill.go:51-56): the predicates only — no score,

@@ -143,6 +143,17 @@ size_t rank_heads_words();
 hipError_t launch_rank_heads(const Conf& cf, const NodeCols& nc, const DevTables& t, const HeadDesc* d_desc, int n_req,
                              bool filt, const PopCtrl* ctrl, int by_score, uint64_t* scratch, int* bx_out,
                              hipStream_t st);
+// kbhip_explain_tasks (kbhip_explain.hip): the verdict byte (node_verdict,
+// kbhip_eval.h) of every node for n_req (1 .. kMaxChunk) tasks of one session
+// and each task's histogram, in one sweep launch (grid (bx, n_req), blockIdx.y
+// = the request, its class d_cls[request] in device memory) and one reduce
+// launch (grid n_req).  verdict: n_req rows of nc.n bytes, or null (no
+// per-node store); part: n_req * bx * 16 words of block counts; out: n_req
+// rows of 16 64-bit bins.  explain_bx: the sweep's grid x for that many
+// requests (cap > 0: at most cap).
+int explain_bx(int n_nodes, int n_req, int cap);
+hipError_t launch_explain(const Conf& cf, const NodeCols& nc, const DevTables& t, const TaskClass* d_cls, int n_req,
+                          int bx, uint8_t* verdict, uint32_t* part, int64_t* out, hipStream_t st);
 // The filtered full walk: a stable compaction of launch_rank_sorted's /
 // launch_rank_radix's output (sorted, *count keys) in three launches — per
 // block of kBlock keys the survivors' count (blk[b]), k_rank_scan over blk

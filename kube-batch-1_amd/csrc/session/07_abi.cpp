@@ -162,6 +162,10 @@ int kbhip_set_option(kb_session* s, const char* key, int64_t value) {
             s->s.overlap = (int)value;
         }
         else if (std::strcmp(key, "rank_radix") == 0) s->s.force_radix = value != 0;
+        else if (std::strcmp(key, "explain_blocks") == 0) {  // kbhip_explain_tasks' grid x at most this (tests)
+            if (value < 0 || value > (1 << 20)) throw kbhip::Error(KBHIP_EINVAL, "explain_blocks must be 0..2^20");
+            s->s.explain_blocks = (int)value;
+        }
         else if (std::strcmp(key, "bf_batch") == 0) s->s.bf_batch = value != 0;
         else if (std::strcmp(key, "aff_batch") == 0) s->s.aff_batch = value != 0;
         else if (std::strcmp(key, "aff_fence") == 0) s->s.aff_fence = value != 0;
@@ -551,6 +555,14 @@ int kbhip_debug_replay(kb_session* s, int32_t n_steps, const int32_t* pods, cons
                 }
             }
         }
+        return KBHIP_OK;
+    })
+}
+int kbhip_debug_explain(kb_session* s, int32_t task_id, uint8_t* out_verdict, int64_t* out_hist) {
+    ABI_GUARD({
+        if (!s || !out_hist) throw kbhip::Error(KBHIP_EINVAL, "null argument");
+        if (!s->s.encode_only) throw kbhip::Error(KBHIP_EINVAL, "kbhip_debug_explain needs an encode-only session");
+        kbhip::debug_explain(s->s, task_id, out_verdict, out_hist);
         return KBHIP_OK;
     })
 }

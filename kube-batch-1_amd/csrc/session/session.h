@@ -650,6 +650,17 @@ struct Session {
     size_t h_heads_in_cap = 0;
     uint64_t* h_heads_out = nullptr;
     size_t h_heads_out_cap = 0;
+    // kbhip_explain_tasks (14_explain.cpp).  h_explain_in (pinned) / b_explain_in: one call's task classes;
+    // b_explain_part: the sweep's block counts [request][block][16]; b_explain_out / h_explain_out (pinned):
+    // the histograms; b_explain_v: the verdict rows of a call that asks for them.  explain_blocks: option
+    // "explain_blocks" (tests; 0 = automatic): the sweep's grid x is at most this.
+    DevBuf b_explain_in, b_explain_part, b_explain_out, b_explain_v;
+    size_t explain_part_words = 0, explain_v_bytes = 0;
+    TaskClass* h_explain_in = nullptr;
+    size_t h_explain_in_cap = 0;
+    int64_t* h_explain_out = nullptr;
+    size_t h_explain_out_cap = 0;
+    int explain_blocks = 0;
     int32_t fallback = -1;  // lowest node index holding a session-placed pod (nodeorder.go:78-93)
     vector<int32_t> sess_cnt;  // per node: session-placed pods on it (fallback after an unpipeline)
     std::unique_ptr<AffinityModel> aff;       // pod (anti-)affinity model (kept for evictions / carry)
@@ -889,6 +900,12 @@ struct Session {
         b_heads_in.release();
         b_heads.release();
         heads_in_cap = 0;
+        if (h_explain_in) MemPool::get().give(MemPool::kPinned, h_explain_in, h_explain_in_cap, device);
+        h_explain_in = nullptr;
+        if (h_explain_out) MemPool::get().give(MemPool::kPinned, h_explain_out, h_explain_out_cap, device);
+        h_explain_out = nullptr;
+        for (DevBuf* b : {&b_explain_in, &b_explain_part, &b_explain_out, &b_explain_v}) b->release();
+        explain_part_words = explain_v_bytes = 0;
         h_out = nullptr;
         if (cu_masked) {  // streams of option "cu_split" are this session's own
             for (int k = 1; k <= kMaxDep; ++k)
@@ -1263,6 +1280,9 @@ int64_t rank_heads_abi(Session& S, const int32_t* task_ids, int n_tasks, bool by
                        int64_t* out_info);
 int64_t apply_ops(Session& S, const uint8_t* op, const int32_t* pod, const int32_t* node, int64_t n,
                   int64_t* out_launches);
+int64_t explain_tasks_abi(Session& S, const int32_t* task_ids, int n_tasks, uint8_t* out_verdict, int64_t* out_hist,
+                          int64_t* out_info);
+void debug_explain(const Session& S, int pod, uint8_t* out_verdict, int64_t* out_hist);
 
 }  // namespace kbhip
 

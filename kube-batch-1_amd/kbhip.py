@@ -23,6 +23,11 @@ STOP_ALL, STOP_UNASSIGNED, STOP_READY = 0, 1, 2
 OP_EVICT, OP_PIPELINE, OP_UNPIPELINE, OP_UNEVICT = 1, 2, 3, 4  # kbhip_apply_ops
 VICTIMS_OTHER_QUEUES, VICTIMS_QUEUE_OTHER_JOBS, VICTIMS_SAME_JOB = 1, 2, 3  # kbhip_rank_victim_nodes
 RANK_HEADS_MAX = 64  # KBHIP_RANK_HEADS_MAX: tasks per kbhip_rank_heads
+# kbhip_explain_tasks: the verdict codes (low four bits of a verdict byte), the short bits of codes 0..2
+(WHY_FITS_IDLE, WHY_FITS_RELEASING, WHY_RESOURCES, WHY_POD_COUNT, WHY_NODE_SELECTOR, WHY_HOST_PORTS,
+ WHY_UNSCHEDULABLE, WHY_TAINTS, WHY_POD_AFFINITY, WHY_SCORE_ERROR) = range(10)
+WHY_SHORT_CPU, WHY_SHORT_MEM, WHY_SHORT_GPU = 0x10, 0x20, 0x40
+EXPLAIN_MAX, EXPLAIN_BINS = 64, 16
 
 # int kbhip_* entry points declared by include/kbhip.h
 EXPORTS = ("kbhip_device_count", "kbhip_session_open", "kbhip_session_open_file", "kbhip_place_job",
@@ -35,7 +40,8 @@ EXPORTS = ("kbhip_device_count", "kbhip_session_open", "kbhip_session_open_file"
            "kbhip_session_carry_events", "kbhip_shard_connect_mailbox", "kbhip_shard_mailbox_fits", "kbhip_place_job_submit",
            "kbhip_place_job_wait", "kbhip_place_job_cancel", "kbhip_time_sweeps", "kbhip_time_rank_multi",
            "kbhip_session_carry_snapshot", "kbhip_walk_visits", "kbhip_fit_deltas", "kbhip_rank_nodes",
-           "kbhip_apply_ops", "kbhip_rank_victim_nodes", "kbhip_rank_heads")
+           "kbhip_apply_ops", "kbhip_rank_victim_nodes", "kbhip_rank_heads", "kbhip_explain_tasks",
+           "kbhip_debug_explain")
 
 RED_MAX_U64, RED_MIN_I64, RED_MAX_I64, RED_SUM_I64 = 0, 1, 2, 3
 ALLREDUCE_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint64), ctypes.c_int32,
@@ -141,6 +147,9 @@ def lib() -> ctypes.CDLL:
         L.kbhip_rank_victim_nodes.restype = i64
         L.kbhip_rank_heads.argtypes = [vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp]
         L.kbhip_rank_heads.restype = i64
+        L.kbhip_explain_tasks.argtypes = [vp, vp, i32, vp, vp, vp]
+        L.kbhip_explain_tasks.restype = i64
+        L.kbhip_debug_explain.argtypes = [vp, i32, vp, vp]
         _lib = L
     return _lib
 
@@ -308,6 +317,34 @@ class Session:
         shape = (n, max(cap, 0))
         return (total[:n].copy(), node[: n * cap].reshape(shape), score[: n * cap].reshape(shape),
                 cands[: n * cap].reshape(shape), info)
+
+    def explain_tasks(self, task_ids, verdicts: bool = False, n_nodes: Optional[int] = None):
+        """kbhip_explain_tasks: why each node is, or is not, in the allocate
+        walk of up to EXPLAIN_MAX pending tasks of the session as it stands:
+        (hist[n, EXPLAIN_BINS], verdict[n, n_nodes] or None, info).  A verdict
+        byte is a WHY_* code, or-ed with the WHY_SHORT_* bits for the codes
+        0..2; hist[i, c] counts the nodes with code c, [11..13] the walk nodes
+        with the cpu / memory / GPU short bit, [14] the walk, [15] the nodes.
+        info (3 int64): kernel launches, the sweep grid's x size, whether
+        verdict rows were written.  verdicts=True needs the node count, which
+        one histogram-only call answers when n_nodes is not given."""
+        ids = np.ascontiguousarray(task_ids, dtype=np.int32).reshape(-1)
+        n = int(ids.size)
+        hist = np.zeros((max(n, 1), EXPLAIN_BINS), np.int64)
+        info = np.zeros(3, np.int64)
+        fn = lib().kbhip_explain_tasks
+        verdict = None
+        if verdicts and n:
+            if n_nodes is None:
+                r = int(fn(self._h, _p(ids), 1, None, _p(hist), None))
+                _check(r if r < 0 else 0)
+                n_nodes = int(hist[0, 15])
+            verdict = np.zeros((n, max(int(n_nodes), 1)), np.uint8)
+        r = int(fn(self._h, _p(ids), n, None if verdict is None else _p(verdict), _p(hist), _p(info)))
+        _check(r if r < 0 else 0)
+        if verdict is not None:
+            verdict = verdict.reshape(-1)[: n * int(n_nodes)].reshape(n, int(n_nodes))
+        return hist[:n].copy(), verdict, info
 
     def apply_ops(self, ops, pods, nodes=None) -> int:
         """kbhip_apply_ops: the evictions and pipelines a host-driven reclaim /
@@ -544,6 +581,15 @@ class EncodedSnapshot:
         if n:
             _check(int(lib().kbhip_debug_table(self._h, name.encode(), _p(out), out.nbytes)))
         return out[: n // np.dtype(dtype).itemsize]
+
+    def explain(self, task_id: int) -> Tuple[np.ndarray, np.ndarray]:
+        """kbhip_debug_explain: (verdict[n_nodes], hist[EXPLAIN_BINS]) of one
+        task, by the kernel's own per-node function on the host tables."""
+        n_nodes = int(self.table("dims")[0])
+        verdict = np.zeros(max(n_nodes, 1), np.uint8)
+        hist = np.zeros(EXPLAIN_BINS, np.int64)
+        _check(lib().kbhip_debug_explain(self._h, int(task_id), _p(verdict), _p(hist)))
+        return verdict[:n_nodes].copy(), hist
 
     def replay(self, pods, modes, nodes, kinds) -> np.ndarray:
         """Per-step, per-node selection keys along a given decision sequence
