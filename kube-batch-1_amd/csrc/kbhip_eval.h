@@ -80,6 +80,21 @@ KBHIP_HD Row load_row(const NodeCols& nc, int n) {
     return r;
 }
 
+// The columns PredicateFn + NodeOrderFn read of a node (41 B: no Idle /
+// Releasing / Backfilled column), loaded a step ahead by the sweeps that
+// prefetch (k_score_sweep_gs, rank_bucket, rank_head).
+struct SweepIn {
+    int64_t acpu, amem, nzc, nzm;
+    int32_t pods, maxtasks;
+    uint8_t fl;
+};
+__device__ __forceinline__ SweepIn sweep_in(const NodeCols& nc, int n) {
+    SweepIn v;
+    v.acpu = nc.acpu[n]; v.amem = nc.amem[n]; v.nzc = nc.nzc[n]; v.nzm = nc.nzm[n];
+    v.pods = nc.pods[n]; v.maxtasks = nc.maxtasks[n]; v.fl = nc.flags[n];
+    return v;
+}
+
 KBHIP_HD bool req_match(const DevTables& t, const NodeCols& nc, const Req& r, int n) {
     // labels.Requirement.Matches (apimachinery/pkg/labels/selector.go:192-236)
     switch (r.op) {

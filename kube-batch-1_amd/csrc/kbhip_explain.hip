@@ -93,17 +93,6 @@ __global__ __launch_bounds__(kBlock) void k_explain_reduce(const uint32_t* part,
     }
 }
 
-static int explain_cus() {
-    static int cus = 0;
-    if (!cus) {
-        int dev = 0;
-        if (hipGetDevice(&dev) != hipSuccess ||
-            hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0)
-            cus = 256;
-    }
-    return cus;
-}
-
 // The sweep's grid x.  One request: a block per 256 nodes, at most one per CU.
 // More requests share kExplainPerCU blocks per CU — what is resident at once
 // at the kernel's register count, so the whole grid is one wave of blocks —
@@ -112,7 +101,7 @@ static int explain_cus() {
 constexpr int kExplainPerCU = 4;
 int explain_bx(int n_nodes, int n_req, int cap) {
     const int need = n_nodes > 0 ? (n_nodes + kBlock - 1) / kBlock : 1;
-    const int cus = explain_cus();
+    const int cus = device_cu_count();
     const int part = n_req > 1 ? kExplainPerCU * cus / n_req : cus;
     int bx = need < part ? need : part;
     if (cap > 0 && bx > cap) bx = cap;

@@ -89,7 +89,12 @@ hipError_t launch_rank_sorted(const Conf& cf, const NodeCols& nc, const DevTable
                               const PopCtrl* ctrl, int by_score, int slo, int shi, uint64_t* keys, uint32_t* hist,
                               uint64_t* sorted, uint32_t* count, hipStream_t st);
 size_t rank_hist_words(int n_nodes);
-// The head of that order without a per-node array (kbhip_rank_nodes): a fused
+// The sort's scan kernel for another translation unit (kbhip_heads.hip): v[0 .. n) becomes its exclusive
+// prefix sum, in one block.
+hipError_t launch_rank_scan(uint32_t* v, int n, hipStream_t st);
+// The current device's compute units (256 when the runtime does not say): what the sweeps size their grids by.
+int device_cu_count();
+// The head of that order without a per-node array (kbhip_heads.hip, kbhip_rank_nodes): a fused
 // predicate + score + top-kTopK sweep, then a one-block merge of the blocks'
 // lists.  Afterwards scratch[0 .. kTopK) = the best keys, descending (0 beyond
 // the passing count), scratch[kTopK] = the passing count; scratch holds
@@ -97,8 +102,6 @@ size_t rank_hist_words(int n_nodes);
 // and the inter-pod prepass, as for launch_rank_nodes.
 int rank_head_blocks(int n_nodes);  // the sweep's grid
 size_t rank_head_words();
-hipError_t launch_rank_head(const Conf& cf, const NodeCols& nc, const DevTables& t, const TaskClass& c,
-                            const PopCtrl* ctrl, int by_score, uint64_t* scratch, hipStream_t st);
 // kbhip_rank_victim_nodes: the walk without the nodes validateVictims
 // (preempt.go:355-370) rejects whatever the plugins answer.  The candidate
 // table (device pointers) holds per queue q and node n the Running tasks with
@@ -118,11 +121,10 @@ struct VictArgs {
     int32_t npad, nq, q, mode, own_n;
     int64_t rc, rm, rg;
 };
-// The filtered head: launch_rank_head with the test above applied by the lane
-// that evaluates the node (scratch as there; the count is the kept nodes').
-hipError_t launch_rank_head_vict(const Conf& cf, const NodeCols& nc, const DevTables& t, const TaskClass& c,
-                                 const PopCtrl* ctrl, int by_score, const VictArgs& v, uint64_t* scratch,
-                                 hipStream_t st);
+// The head's launch; v non-null (kbhip_rank_victim_nodes): the test above applied by the lane that
+// evaluates the node (the count is the kept nodes').
+hipError_t launch_rank_head(const Conf& cf, const NodeCols& nc, const DevTables& t, const TaskClass& c,
+                            const PopCtrl* ctrl, int by_score, const VictArgs* v, uint64_t* scratch, hipStream_t st);
 // kbhip_rank_heads: the heads of n_req (1 .. kMaxChunk) tasks of one session in
 // one sweep launch (grid (bx, n_req), blockIdx.y = the request) and one merge
 // launch (grid n_req).  Request r is d_desc[r] in device memory: its class,

@@ -640,11 +640,7 @@ int kbhip_time_rank_multi(kb_session* const* sessions, int32_t n, const int32_t*
 
 int kbhip_sweep_scores(kb_session* s, int32_t task_id, uint64_t* out_keys) {
     ABI_GUARD_S(s, {
-        if (!s) throw kbhip::Error(KBHIP_EINVAL, "null session");
-        if (s->s.encode_only) throw kbhip::Error(KBHIP_EINVAL, "encode-only session has no device state");
-        kbhip::require_no_tickets(s->s);
-        HIPCHK(hipSetDevice(s->s.device));
-        return kbhip::sweep_scores(s->s, task_id, out_keys);
+        return kbhip::sweep_scores(kbhip::device_session(s), task_id, out_keys);
     })
 }
 

@@ -240,19 +240,14 @@ void carry_snapshot(kb_session* ks, const kbs::Snapshot& s, const int32_t* old_p
     add_col(S.nc.flags, sizeof(uint8_t));
     for (int w = 0; w < S.nc.port_words; ++w) add_col(S.nc.ports + (size_t)w * S.nc.npad, sizeof(uint64_t));
     struct Stage {  // pooled pinned buffer, returned on every exit (after the stream has drained)
+        PinnedBuf buf;
         uint8_t* p = nullptr;
-        size_t cap = 0;
-        int dev = 0;
         hipStream_t st = nullptr;
-        ~Stage() {
-            if (!p) return;
-            (void)hipStreamSynchronize(st);
-            MemPool::get().give(MemPool::kPinned, p, cap, dev);
-        }
+        ~Stage() { if (p) (void)hipStreamSynchronize(st); }
     } stage;
-    stage.dev = S.device;
     stage.st = S.stream;
-    stage.p = (uint8_t*)MemPool::get().take(MemPool::kPinned, std::max<size_t>(stage_bytes, 256), &stage.cap);
+    stage.buf.fit(std::max<size_t>(stage_bytes, 256));
+    stage.p = stage.buf.as<uint8_t>();
     for (auto& c : dcols)
         HIPCHK(hipMemcpyAsync(stage.p + c.off, c.d, (size_t)Nl * c.elem, hipMemcpyDeviceToHost, S.stream));
     // ---------------- nodes: allocatable, pods, unschedulable (labels / taints unchanged) ----------------

@@ -6,11 +6,7 @@ using namespace kbhip;
 extern "C" {
 int kbhip_session_carry(kb_session* s, int64_t* out_uploaded_bytes) {
     ABI_GUARD_S(s, {
-        if (!s) throw kbhip::Error(KBHIP_EINVAL, "null session");
-        if (s->s.encode_only) throw kbhip::Error(KBHIP_EINVAL, "encode-only session has no device state");
-        kbhip::require_no_tickets(s->s);
-        HIPCHK(hipSetDevice(s->s.device));
-        session_carry(s->s);
+        session_carry(kbhip::device_session(s));
         if (out_uploaded_bytes) *out_uploaded_bytes = s->s.carry_bytes;
         return 0;
     })
@@ -18,12 +14,8 @@ int kbhip_session_carry(kb_session* s, int64_t* out_uploaded_bytes) {
 int kbhip_session_carry_events(kb_session* s, const int32_t* pods, const uint8_t* events, int64_t n,
                                int64_t* out_uploaded_bytes) {
     ABI_GUARD_S(s, {
-        if (!s) throw kbhip::Error(KBHIP_EINVAL, "null session");
         if (n < 0 || (n > 0 && (!pods || !events))) throw kbhip::Error(KBHIP_EINVAL, "null argument");
-        if (s->s.encode_only) throw kbhip::Error(KBHIP_EINVAL, "encode-only session has no device state");
-        kbhip::require_no_tickets(s->s);
-        HIPCHK(hipSetDevice(s->s.device));
-        session_carry(s->s, pods, events, n);
+        session_carry(kbhip::device_session(s), pods, events, n);
         if (out_uploaded_bytes) *out_uploaded_bytes = s->s.carry_bytes;
         return 0;
     })

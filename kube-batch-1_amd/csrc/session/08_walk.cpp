@@ -116,25 +116,17 @@ extern "C" {
 
 int64_t kbhip_walk_visits(kb_session* s, int32_t* out_node, uint32_t* out_count, int64_t cap) {
     ABI_GUARD_S(s, {
-        if (!s) throw kbhip::Error(KBHIP_EINVAL, "null session");
         if (cap < 0 || (cap > 0 && (!out_node || !out_count)))
             throw kbhip::Error(KBHIP_EINVAL, "null output array with cap > 0");
-        if (s->s.encode_only) throw kbhip::Error(KBHIP_EINVAL, "encode-only session has no device state");
-        kbhip::require_no_tickets(s->s);
-        HIPCHK(hipSetDevice(s->s.device));
-        return kbhip::walk_visits(s->s, out_node, out_count, cap);
+        return kbhip::walk_visits(kbhip::device_session(s), out_node, out_count, cap);
     })
 }
 
 int64_t kbhip_fit_deltas(kb_session* s, int32_t task_id, int32_t* out_node, int64_t* out_delta, int64_t cap) {
     ABI_GUARD_S(s, {
-        if (!s) throw kbhip::Error(KBHIP_EINVAL, "null session");
         if (cap < 0 || (cap > 0 && (!out_node || !out_delta)))
             throw kbhip::Error(KBHIP_EINVAL, "null output array with cap > 0");
-        if (s->s.encode_only) throw kbhip::Error(KBHIP_EINVAL, "encode-only session has no device state");
-        kbhip::require_no_tickets(s->s);
-        HIPCHK(hipSetDevice(s->s.device));
-        return kbhip::fit_deltas(s->s, task_id, out_node, out_delta, cap);
+        return kbhip::fit_deltas(kbhip::device_session(s), task_id, out_node, out_delta, cap);
     })
 }
 

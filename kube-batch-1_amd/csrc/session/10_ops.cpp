@@ -128,22 +128,14 @@ static int launch_node_ops(Session& S, const vector<NodeOp>& ops) {
                  bytes = o_q + (vict ? align8(M * sizeof(int32_t)) : 0);
     if (!S.ev_ops) HIPCHK(hipEventCreateWithFlags(&S.ev_ops, hipEventDisableTiming));
     else HIPCHK(hipEventSynchronize(S.ev_ops));  // the previous call's copy has read the staging
-    if (S.h_ops_cap < bytes) {
-        if (S.h_ops) MemPool::get().give(MemPool::kPinned, S.h_ops, S.h_ops_cap, S.device);
-        S.h_ops = nullptr;
-        S.h_ops_cap = 0;
-        S.h_ops = (uint8_t*)MemPool::get().take(MemPool::kPinned, std::max<size_t>(bytes + bytes / 2, 4096), &S.h_ops_cap);
-    }
-    if (S.b_ops_bytes < bytes) {  // growth only: the old block goes back to the pool once its last reader ended
-        if (S.b_ops.p) HIPCHK(hipStreamSynchronize(S.stream));
-        S.b_ops_bytes = std::max<size_t>(bytes + bytes / 2, 4096);
-        S.b_ops.alloc<uint8_t>(S.b_ops_bytes);
-    }
-    int64_t* h_req = (int64_t*)(S.h_ops + o_req);
-    int32_t* h_node = (int32_t*)(S.h_ops + o_node);
-    int32_t* h_off = (int32_t*)(S.h_ops + o_off);
-    int32_t* h_kc = (int32_t*)(S.h_ops + o_kc);
-    int32_t* h_q = vict ? (int32_t*)(S.h_ops + o_q) : nullptr;
+    S.h_ops.fit(bytes, std::max<size_t>(bytes + bytes / 2, 4096));
+    S.b_ops.grow(S.stream, bytes, std::max<size_t>(bytes + bytes / 2, 4096));
+    uint8_t* const h = S.h_ops.as<uint8_t>();
+    int64_t* h_req = (int64_t*)(h + o_req);
+    int32_t* h_node = (int32_t*)(h + o_node);
+    int32_t* h_off = (int32_t*)(h + o_off);
+    int32_t* h_kc = (int32_t*)(h + o_kc);
+    int32_t* h_q = vict ? (int32_t*)(h + o_q) : nullptr;
     int32_t run = 0;
     for (size_t d = 0; d < D; ++d) {
         h_node[d] = seg_node[d] - S.nc.base;  // (one-GPU sessions: base 0)
@@ -159,7 +151,7 @@ static int launch_node_ops(Session& S, const vector<NodeOp>& ops) {
         if (h_q) h_q[j] = o.queue;
     }
     uint8_t* d = (uint8_t*)S.b_ops.p;
-    HIPCHK(hipMemcpyAsync(d, S.h_ops, bytes, hipMemcpyHostToDevice, S.stream));
+    HIPCHK(hipMemcpyAsync(d, h, bytes, hipMemcpyHostToDevice, S.stream));
     HIPCHK(hipEventRecord(S.ev_ops, S.stream));
     ApplyOps a{(const int32_t*)(d + o_node), (const int32_t*)(d + o_off), (const int32_t*)(d + o_kc),
                (const int64_t*)(d + o_req), (int)D, vict ? (const int32_t*)(d + o_q) : nullptr,
@@ -203,13 +195,9 @@ extern "C" {
 int64_t kbhip_apply_ops(kb_session* s, const uint8_t* op, const int32_t* pod, const int32_t* node, int64_t n,
                         int64_t* out_launches) {
     ABI_GUARD_S(s, {
-        if (!s) throw kbhip::Error(KBHIP_EINVAL, "null session");
         if (n < 0 || (n > 0 && (!op || !pod || !node)))
             throw kbhip::Error(KBHIP_EINVAL, "kbhip_apply_ops: negative n, or a null op / pod / node array with n > 0");
-        if (s->s.encode_only) throw kbhip::Error(KBHIP_EINVAL, "encode-only session has no device state");
-        kbhip::require_no_tickets(s->s);
-        HIPCHK(hipSetDevice(s->s.device));
-        return kbhip::apply_ops(s->s, op, pod, node, n, out_launches);
+        return kbhip::apply_ops(kbhip::device_session(s), op, pod, node, n, out_launches);
     })
 }
 

@@ -14,7 +14,7 @@ void rank_buffers(Session& S) {
     S.rank_tmp_bytes = std::max<size_t>((size_t)16, rank_hist_words(N) * sizeof(uint32_t));
     S.b_rank_tmp.alloc<uint8_t>(S.rank_tmp_bytes);
     S.b_rank_radix.alloc<uint64_t>(std::max(N, 1));
-    S.h_rank = (uint64_t*)MemPool::get().take(MemPool::kPinned, (size_t)(N + 1) * sizeof(uint64_t), &S.h_rank_cap);
+    S.h_rank.fit((size_t)(N + 1) * sizeof(uint64_t));
 }
 
 // The device ranking of the task class cls on the session's stream: the keys
@@ -22,15 +22,19 @@ void rank_buffers(Session& S) {
 // descending in b_rank_sorted, the passing count in b_rank_cnt[0] and the
 // nodes whose score left the class's range in b_rank_cnt[1].  Nothing is
 // copied back or waited for (the what-if batcher's shared launch aside).
-void rank_launch(Session& S, int cls, bool by_score) {
+// Returns the kernel launches it made (the batcher's shared launch counted as
+// the session's own three).
+int rank_launch(Session& S, int cls, bool by_score) {
     const int N = S.nc.n;
     rank_buffers(S);
-    flush_tables(S);  // evictions / unevicts so far change pod-affinity predicates
+    int launches = flush_tables(S);  // evictions / unevicts so far change pod-affinity predicates
     ctrl_setup(S, 1, &cls, 0, 0, 0, 0, -1, 0);
+    launches += 1;
     HIPCHK(hipMemsetAsync(S.b_rank_cnt.p, 0, 2 * sizeof(uint32_t), S.stream));
     auto sr = S.class_srange[cls];
     if (by_score && S.classes[cls].ipa_n > 0) {  // inter-pod priority: normalisation prepass, wider range
         HIPCHK(launch_ipa_minmax(S.nc, S.tab, S.d_ctrl, 0, S.stream));
+        launches += 1;
         exchange(S, &S.d_ctrl->ipa_lo[0], KBHIP_RED_MIN_I64);  // (shards: over every node)
         exchange(S, &S.d_ctrl->ipa_hi[0], KBHIP_RED_MAX_I64);
         const int64_t w = 10 * (int64_t)S.conf.w_pa * S.conf.score_mult;
@@ -53,28 +57,33 @@ void rank_launch(Session& S, int cls, bool by_score) {
         HIPCHK(r.err);
         S.stats.rank_requests++;
         S.stats.rank_batch_sum += r.batch;
+        launches += 3;
     } else if (counting) {  // hand-written stable counting sort over the score
         HIPCHK(launch_rank_sorted(S.conf, S.nc, S.tab, S.classes[cls], S.d_ctrl, by_score ? 1 : 0, (int)sr.first,
                                   (int)sr.second,
                                   (uint64_t*)S.b_rank_keys.p, (uint32_t*)S.b_rank_tmp.p,
                                   (uint64_t*)S.b_rank_sorted.p, (uint32_t*)S.b_rank_cnt.p, S.stream));
+        launches += 3;  // bucket, scan, scatter
     } else {  // wide score ranges (large nodeorder weights): 8-bit LSD radix passes over the score
         HIPCHK(launch_rank_nodes(S.conf, S.nc, S.tab, S.d_ctrl, by_score ? 1 : 0, (uint64_t*)S.b_rank_keys.p,
                                  (uint32_t*)S.b_rank_cnt.p, S.stream));
         HIPCHK(launch_rank_radix((const uint64_t*)S.b_rank_keys.p, N, (const uint32_t*)S.b_rank_cnt.p,
                                  (uint32_t*)S.b_rank_tmp.p, (uint64_t*)S.b_rank_radix.p,
                                  (uint64_t*)S.b_rank_sorted.p, S.stream));
+        launches += 1 + 4 * 3;  // the key sweep, then four passes of bucket, scan, scatter
     }
+    return launches;
 }
 
 // Node-sharded ranking: every shard's sorted passing keys (descending; global node index
 // inside) all-gathered as fixed-size records [count, keys...], merged into the order one
 // GPU's sort of every node gives (the keys are distinct).
 static void merge_shard_ranks(Session& S, int cnt, vector<int>& out) {
+    const uint64_t* const h_rank = S.h_rank.as<uint64_t>();
     const size_t rec = (size_t)(S.n_total + S.world - 1) / S.world + 1;  // >= every shard's rows + 1
     vector<uint64_t> send(rec, 0), recv(rec * S.world);
     send[0] = (uint64_t)cnt;
-    std::memcpy(send.data() + 1, S.h_rank + 1, (size_t)cnt * sizeof(uint64_t));
+    std::memcpy(send.data() + 1, h_rank + 1, (size_t)cnt * sizeof(uint64_t));
     gather_host(S, send.data(), recv.data(), rec * sizeof(uint64_t));
     vector<size_t> at(S.world), end(S.world);
     size_t total = 0;
@@ -96,15 +105,16 @@ static void merge_shard_ranks(Session& S, int cnt, vector<int>& out) {
 static void rank_nodes_inner(Session& S, int cls, bool by_score, vector<int>& out) {
     const int N = S.nc.n;
     rank_launch(S, cls, by_score);
+    uint64_t* const h_rank = S.h_rank.as<uint64_t>();
     const int first = std::min(N, S.rank_first);
-    HIPCHK(hipMemcpyAsync(S.h_rank, S.b_rank_cnt.p, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, S.stream));
-    HIPCHK(hipMemcpyAsync(S.h_rank + 1, S.b_rank_sorted.p, first * sizeof(uint64_t), hipMemcpyDeviceToHost,
+    HIPCHK(hipMemcpyAsync(h_rank, S.b_rank_cnt.p, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, S.stream));
+    HIPCHK(hipMemcpyAsync(h_rank + 1, S.b_rank_sorted.p, first * sizeof(uint64_t), hipMemcpyDeviceToHost,
                           S.stream));
     HIPCHK(hipStreamSynchronize(S.stream));
-    const int cnt = (int)(uint32_t)S.h_rank[0];
-    if (S.h_rank[0] >> 32) throw Error(KBHIP_EDEVICE, "rank_nodes: node score outside the class score range");
+    const int cnt = (int)(uint32_t)h_rank[0];
+    if (h_rank[0] >> 32) throw Error(KBHIP_EDEVICE, "rank_nodes: node score outside the class score range");
     if (cnt > first) {
-        HIPCHK(hipMemcpyAsync(S.h_rank + 1 + first, (const uint64_t*)S.b_rank_sorted.p + first,
+        HIPCHK(hipMemcpyAsync(h_rank + 1 + first, (const uint64_t*)S.b_rank_sorted.p + first,
                               (size_t)(cnt - first) * sizeof(uint64_t), hipMemcpyDeviceToHost, S.stream));
         HIPCHK(hipStreamSynchronize(S.stream));
     }
@@ -112,7 +122,7 @@ static void rank_nodes_inner(Session& S, int cls, bool by_score, vector<int>& ou
         merge_shard_ranks(S, cnt, out);
     } else {
         out.resize(cnt);
-        for (int i = 0; i < cnt; ++i) out[i] = key_idx(S.h_rank[1 + i]);
+        for (int i = 0; i < cnt; ++i) out[i] = key_idx(h_rank[1 + i]);
     }
     S.stats.sweeps++;
     S.stats.tasks++;

@@ -1,4 +1,5 @@
-// kbhip session, part 12: the victim-candidate table and the pruned node walk (kbhip_rank_victim_nodes)
+// kbhip session, part 12: the ranked node walk of one task (kbhip_rank_nodes), the victim-candidate table and
+// the walk pruned by it (kbhip_rank_victim_nodes)
 #include "framework.h"
 
 namespace kbhip {
@@ -85,7 +86,7 @@ void vict_own_list(const Session& S, int jb, vector<int32_t>& node, vector<int64
     }
 }
 
-// vict_cand of kbhip_evict.hip on the host copy: the candidate count of node n
+// vict_cand of kbhip_heads.hip on the host copy: the candidate count of node n
 int64_t vict_count_host(const Session& S, int mode, int q, const vector<int32_t>& own_node,
                         const vector<int64_t>& own_sum, int n) {
     const size_t np = (size_t)S.nc.npad, Q = S.queues.size();
@@ -111,128 +112,116 @@ void vict_apply_evictions(Session& S, const vector<NodeOp>& ops) {
     }
 }
 
-// kbhip_rank_nodes' walk (09_rank.cpp) without the nodes whose victim
-// candidates of `mode` are none, or together strictly short of the task's
-// InitResreq in all three resources.  The head (first + cap <= kTopK) is one
-// filtered sweep (launch_rank_head_vict) with the candidate counts of the
-// returned nodes taken from the host copy of the table; anything else is the
-// actions' full sort followed by a stable compaction (launch_vict_compact), of
-// which the count and then the window asked for are copied back.
+// Entries [first, first + cap) of the walk order of task `pod` (by_score:
+// preempt's SelectBestNode order, else reclaim's index order) and the number
+// of nodes in it.  mode 0 (kbhip_rank_nodes): every node of the order.  mode
+// KBHIP_VICTIMS_* (kbhip_rank_victim_nodes): without the nodes whose victim
+// candidates of that mode are none, or together strictly short of the task's
+// InitResreq in all three resources; the victim-candidate table is built
+// unless it is live, the job's own list goes up, and the window's candidate
+// counts come back.  The head of the walk (first + cap <= kTopK) is one fused
+// top-kTopK sweep (launch_rank_head, filtered by the lane that evaluates the
+// node: nothing of size N written, kTopK keys and the count copied back, the
+// candidate counts of the returned nodes taken from the host copy of the
+// table); anything else is the full device sort of the reclaim / preempt
+// actions (rank_launch), followed in a victim mode by a stable compaction
+// (launch_vict_compact), of which the count and then only the window asked
+// for are copied.  Reads the session state and changes nothing but the
+// table's liveness; nothing is kept for a later call.
 int64_t rank_victim_nodes_abi(Session& S, int pod, bool by_score, int mode, int64_t first, int32_t* out_node,
                               int32_t* out_score, int32_t* out_cands, int64_t cap, int64_t* out_info) {
-    if (pod < 0 || pod >= (int)S.pods.size() || S.pods[pod].cls < 0)
-        throw Error(KBHIP_EINVAL, "task id has no task class (not a pending task of the session)");
-    if (S.pods[pod].status != Pending)
-        throw Error(KBHIP_EINVAL, "kbhip_rank_victim_nodes: the task is not Pending (the session placed it)");
-    const int jb = S.pods[pod].job;
-    if (jb < 0 || S.jobs[jb].queue < 0 || S.jobs[jb].queue >= (int)S.queues.size())
-        throw Error(KBHIP_EINVAL, "kbhip_rank_victim_nodes: the task has no job");
-    if (S.world != 1) throw Error(KBHIP_EUNSUPPORTED, "kbhip_rank_victim_nodes on a node-sharded session");
-    ov_quiesce(S);
-    const int cls = S.pods[pod].cls, N = S.nc.n;
-    const bool rebuilt = vict_ensure(S);
+    const char* const api = mode ? "kbhip_rank_victim_nodes" : "kbhip_rank_nodes";
+    const HPod& p = query_task(S, pod, string(api) + ": the task ", mode != 0, "task id ");
+    query_begin(S, api);
+    const int cls = p.cls, N = S.nc.n;
+    const bool rebuilt = mode != 0 && vict_ensure(S);
     vector<int32_t> own_node;
     vector<int64_t> own_sum;
-    if (mode != KBHIP_VICTIMS_OTHER_QUEUES) vict_own_list(S, jb, own_node, own_sum);
+    if (mode != 0 && mode != KBHIP_VICTIMS_OTHER_QUEUES) vict_own_list(S, p.job, own_node, own_sum);
     const size_t own_n = own_node.size(), own_bytes = own_n * (4 * sizeof(int64_t) + sizeof(int32_t));
     if (own_n) {  // sums, then nodes, in one copy (the previous call's copy ended with that call)
-        if (S.h_vict_own_cap < own_bytes) {
-            if (S.h_vict_own) MemPool::get().give(MemPool::kPinned, S.h_vict_own, S.h_vict_own_cap, S.device);
-            S.h_vict_own = nullptr;
-            S.h_vict_own_cap = 0;
-            S.h_vict_own = (uint8_t*)MemPool::get().take(MemPool::kPinned, std::max<size_t>(2 * own_bytes, 4096),
-                                                          &S.h_vict_own_cap);
-        }
-        if (S.vict_own_cap < own_bytes) {
-            HIPCHK(hipStreamSynchronize(S.stream));
-            S.vict_own_cap = std::max<size_t>(2 * own_bytes, 4096);
-            S.b_vict_own.alloc<uint8_t>(S.vict_own_cap);
-        }
-        std::memcpy(S.h_vict_own, own_sum.data(), own_n * 4 * sizeof(int64_t));
-        std::memcpy(S.h_vict_own + own_n * 4 * sizeof(int64_t), own_node.data(), own_n * sizeof(int32_t));
-        HIPCHK(hipMemcpyAsync(S.b_vict_own.p, S.h_vict_own, own_bytes, hipMemcpyHostToDevice, S.stream));
+        S.h_vict_own.fit(own_bytes, std::max<size_t>(2 * own_bytes, 4096));
+        S.b_vict_own.grow(S.stream, own_bytes, std::max<size_t>(2 * own_bytes, 4096));
+        uint8_t* const h_own = S.h_vict_own.as<uint8_t>();
+        std::memcpy(h_own, own_sum.data(), own_n * 4 * sizeof(int64_t));
+        std::memcpy(h_own + own_n * 4 * sizeof(int64_t), own_node.data(), own_n * sizeof(int32_t));
+        HIPCHK(hipMemcpyAsync(S.b_vict_own.p, h_own, own_bytes, hipMemcpyHostToDevice, S.stream));
     }
-    const R3& ireq = S.pods[pod].ireq;
-    const uint8_t* d_own = (const uint8_t*)S.b_vict_own.p;
-    const VictArgs v{(const int64_t*)S.b_vict.p,
+    VictArgs v{};
+    if (mode != 0) {
+        const uint8_t* d_own = (const uint8_t*)S.b_vict_own.p;
+        v = VictArgs{(const int64_t*)S.b_vict.p,
                      own_n ? (const int32_t*)(d_own + own_n * 4 * sizeof(int64_t)) : nullptr,
                      own_n ? (const int64_t*)d_own : nullptr,
-                     S.nc.npad, (int32_t)S.queues.size(), S.jobs[jb].queue, mode, (int32_t)own_n,
-                     ireq.c, ireq.m, ireq.g};
+                     S.nc.npad, (int32_t)S.queues.size(), S.jobs[p.job].queue, mode, (int32_t)own_n,
+                     p.ireq.c, p.ireq.m, p.ireq.g};
+        S.h_vict_out.fit(((size_t)N + 2) * sizeof(int32_t));
+    }
+    int32_t* const h_out = S.h_vict_out.as<int32_t>();  // victim modes: [0] the kept count, then the window's counts
     const TaskClass& c = S.classes[cls];
-    const bool ipa = by_score && c.ipa_n > 0;
-    const uint64_t* keys = nullptr;
-    const int32_t* cands = nullptr;
+    const uint64_t* keys = nullptr;  // entries [first, first + n_keys) of the order, on the host
     int64_t total = 0, n_keys = 0, launches = flush_tables(S);  // evictions / unevicts so far change pod-affinity predicates
     const bool head = cap > 0 && first <= kTopK && cap <= kTopK - first;
-    if (!S.h_vict_out || S.h_vict_out_cap < ((size_t)N + 2) * sizeof(int32_t)) {
-        if (S.h_vict_out) MemPool::get().give(MemPool::kPinned, S.h_vict_out, S.h_vict_out_cap, S.device);
-        S.h_vict_out = nullptr;
-        S.h_vict_out = (int32_t*)MemPool::get().take(MemPool::kPinned, ((size_t)N + 2) * sizeof(int32_t),
-                                                     &S.h_vict_out_cap);
-    }
     if (head) {
         if (!S.b_rank_head.p) S.b_rank_head.alloc<uint64_t>(rank_head_words());
-        if (!S.h_rank_head)
-            S.h_rank_head = (uint64_t*)MemPool::get().take(MemPool::kPinned, (size_t)(kTopK + 1) * sizeof(uint64_t),
-                                                           &S.h_rank_head_cap);
+        S.h_rank_head.fit((size_t)(kTopK + 1) * sizeof(uint64_t));
+        uint64_t* const h_head = S.h_rank_head.as<uint64_t>();
         ctrl_setup(S, 1, &cls, 0, 0, 0, 0, -1, 0);
-        if (ipa) HIPCHK(launch_ipa_minmax(S.nc, S.tab, S.d_ctrl, 0, S.stream));
-        HIPCHK(launch_rank_head_vict(S.conf, S.nc, S.tab, c, S.d_ctrl, by_score ? 1 : 0, v,
-                                     (uint64_t*)S.b_rank_head.p, S.stream));
-        HIPCHK(hipMemcpyAsync(S.h_rank_head, S.b_rank_head.p, (size_t)(kTopK + 1) * sizeof(uint64_t),
-                              hipMemcpyDeviceToHost, S.stream));
-        HIPCHK(hipStreamSynchronize(S.stream));
-        total = (int64_t)S.h_rank_head[kTopK];
-        n_keys = first < total ? std::min(cap, total - first) : 0;
-        keys = S.h_rank_head + first;
-        for (int64_t i = 0; i < n_keys; ++i)
-            S.h_vict_out[1 + i] = (int32_t)vict_count_host(S, mode, v.q, own_node, own_sum, key_idx(keys[i]));
-        cands = S.h_vict_out + 1;
-        launches += 1 + (ipa ? 1 : 0) + 2;  // the control block, the inter-pod prepass, sweep + merge
-    } else {
-        rank_launch(S, cls, by_score);
-        if (!S.b_vict_keys.p) {
-            S.b_vict_keys.alloc<uint64_t>(std::max(N, 1));
-            S.b_vict_cands.alloc<int32_t>(std::max(N, 1));
-            S.b_vict_blk.alloc<uint32_t>((size_t)vict_blocks(N) + 1);
+        launches += 1;
+        if (by_score && c.ipa_n > 0) {
+            HIPCHK(launch_ipa_minmax(S.nc, S.tab, S.d_ctrl, 0, S.stream));
+            launches += 1;
         }
-        HIPCHK(launch_vict_compact((const uint64_t*)S.b_rank_sorted.p, (const uint32_t*)S.b_rank_cnt.p, N, v,
-                                   (uint32_t*)S.b_vict_blk.p, (uint64_t*)S.b_vict_keys.p,
-                                   (int32_t*)S.b_vict_cands.p, S.stream));
-        HIPCHK(hipMemcpyAsync(S.h_rank, S.b_rank_cnt.p, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, S.stream));
-        HIPCHK(hipMemcpyAsync(S.h_vict_out, (const uint32_t*)S.b_vict_blk.p + vict_blocks(N), sizeof(uint32_t),
-                              hipMemcpyDeviceToHost, S.stream));
+        HIPCHK(launch_rank_head(S.conf, S.nc, S.tab, c, S.d_ctrl, by_score ? 1 : 0, mode ? &v : nullptr,
+                                (uint64_t*)S.b_rank_head.p, S.stream));
+        launches += 2;  // sweep + merge
+        HIPCHK(hipMemcpyAsync(h_head, S.b_rank_head.p, (size_t)(kTopK + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost,
+                              S.stream));
         HIPCHK(hipStreamSynchronize(S.stream));
-        if (S.h_rank[0] >> 32)
-            throw Error(KBHIP_EDEVICE, "rank_victim_nodes: node score outside the class score range");
-        total = (int64_t)(uint32_t)S.h_vict_out[0];
+        total = (int64_t)h_head[kTopK];
+        n_keys = first < total ? std::min(cap, total - first) : 0;
+        keys = h_head + first;
+        for (int64_t i = 0; mode != 0 && i < n_keys; ++i)
+            h_out[1 + i] = (int32_t)vict_count_host(S, mode, v.q, own_node, own_sum, key_idx(keys[i]));
+        if (mode == 0) S.stats.rank_heads++;
+    } else {
+        launches += rank_launch(S, cls, by_score);
+        const uint64_t* d_keys = (const uint64_t*)S.b_rank_sorted.p;  // the order the window is read from
+        uint64_t* const h_rank = S.h_rank.as<uint64_t>();
+        if (mode != 0) {
+            if (!S.b_vict_keys.p) {
+                S.b_vict_keys.alloc<uint64_t>(std::max(N, 1));
+                S.b_vict_cands.alloc<int32_t>(std::max(N, 1));
+                S.b_vict_blk.alloc<uint32_t>((size_t)vict_blocks(N) + 1);
+            }
+            HIPCHK(launch_vict_compact(d_keys, (const uint32_t*)S.b_rank_cnt.p, N, v, (uint32_t*)S.b_vict_blk.p,
+                                       (uint64_t*)S.b_vict_keys.p, (int32_t*)S.b_vict_cands.p, S.stream));
+            launches += 3;
+            d_keys = (const uint64_t*)S.b_vict_keys.p;
+            HIPCHK(hipMemcpyAsync(h_out, (const uint32_t*)S.b_vict_blk.p + vict_blocks(N), sizeof(uint32_t),
+                                  hipMemcpyDeviceToHost, S.stream));
+        }
+        HIPCHK(hipMemcpyAsync(h_rank, S.b_rank_cnt.p, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, S.stream));
+        HIPCHK(hipStreamSynchronize(S.stream));
+        if (h_rank[0] >> 32)  // (the text names the call without its "kbhip_")
+            throw Error(KBHIP_EDEVICE, string(api + 6) + ": node score outside the class score range");
+        total = mode != 0 ? (int64_t)(uint32_t)h_out[0] : (int64_t)(uint32_t)h_rank[0];
         n_keys = first < total ? std::min(cap, total - first) : 0;
         if (n_keys > 0) {
-            HIPCHK(hipMemcpyAsync(S.h_rank + 1, (const uint64_t*)S.b_vict_keys.p + first,
-                                  (size_t)n_keys * sizeof(uint64_t), hipMemcpyDeviceToHost, S.stream));
-            HIPCHK(hipMemcpyAsync(S.h_vict_out + 1, (const int32_t*)S.b_vict_cands.p + first,
-                                  (size_t)n_keys * sizeof(int32_t), hipMemcpyDeviceToHost, S.stream));
+            HIPCHK(hipMemcpyAsync(h_rank + 1, d_keys + first, (size_t)n_keys * sizeof(uint64_t), hipMemcpyDeviceToHost,
+                                  S.stream));
+            if (mode != 0)
+                HIPCHK(hipMemcpyAsync(h_out + 1, (const int32_t*)S.b_vict_cands.p + first,
+                                      (size_t)n_keys * sizeof(int32_t), hipMemcpyDeviceToHost, S.stream));
             HIPCHK(hipStreamSynchronize(S.stream));
         }
-        keys = S.h_rank + 1;
-        cands = S.h_vict_out + 1;
-        // rank_launch's own launches (11_evict.cpp): the control block, the inter-pod prepass, then the
-        // counting sort's three kernels or the key sweep and four radix passes of three; then the compaction's three
-        auto sr = S.class_srange[cls];
-        if (ipa) {
-            const int64_t w = 10 * (int64_t)S.conf.w_pa * S.conf.score_mult;
-            sr.first += std::min<int64_t>(0, w);
-            sr.second += std::max<int64_t>(0, w);
-        }
-        const bool counting = !S.force_radix && sr.second - sr.first < 256 && sr.first >= INT32_MIN &&
-                              sr.second <= INT32_MAX;
-        launches += 1 + (ipa ? 1 : 0) + (counting ? 3 : 13) + 3;
+        keys = h_rank + 1;
+        if (mode == 0) S.stats.rank_fulls++;
     }
     for (int64_t i = 0; i < n_keys; ++i) {
         out_node[i] = key_idx(keys[i]);
         if (out_score) out_score[i] = by_score ? key_score(keys[i]) : 0;
-        if (out_cands) out_cands[i] = cands[i];
+        if (out_cands) out_cands[i] = h_out[1 + i];
     }
     if (out_info) {
         out_info[0] = head ? 1 : 0;
@@ -249,11 +238,21 @@ using namespace kbhip;
 
 extern "C" {
 
+int64_t kbhip_rank_nodes(kb_session* s, int32_t task_id, int32_t by_score, int64_t first, int32_t* out_node,
+                         int32_t* out_score, int64_t cap) {
+    ABI_GUARD_S(s, {
+        if (first < 0 || cap < 0 || (cap > 0 && !out_node))
+            throw kbhip::Error(KBHIP_EINVAL, "kbhip_rank_nodes: negative first or cap, or null out_node with cap > 0");
+        if (by_score != 0 && by_score != 1) throw kbhip::Error(KBHIP_EINVAL, "kbhip_rank_nodes: by_score is 0 or 1");
+        return kbhip::rank_victim_nodes_abi(kbhip::device_session(s), task_id, by_score != 0, 0, first, out_node,
+                                            out_score, nullptr, cap, nullptr);
+    })
+}
+
 int64_t kbhip_rank_victim_nodes(kb_session* s, int32_t task_id, int32_t by_score, int32_t victims, int64_t first,
                                 int32_t* out_node, int32_t* out_score, int32_t* out_cands, int64_t cap,
                                 int64_t* out_info) {
     ABI_GUARD_S(s, {
-        if (!s) throw kbhip::Error(KBHIP_EINVAL, "null session");
         if (first < 0 || cap < 0 || (cap > 0 && !out_node))
             throw kbhip::Error(KBHIP_EINVAL,
                                "kbhip_rank_victim_nodes: negative first or cap, or null out_node with cap > 0");
@@ -261,11 +260,8 @@ int64_t kbhip_rank_victim_nodes(kb_session* s, int32_t task_id, int32_t by_score
             throw kbhip::Error(KBHIP_EINVAL, "kbhip_rank_victim_nodes: by_score is 0 or 1");
         if (victims < KBHIP_VICTIMS_OTHER_QUEUES || victims > KBHIP_VICTIMS_SAME_JOB)
             throw kbhip::Error(KBHIP_EINVAL, "kbhip_rank_victim_nodes: victims is one of KBHIP_VICTIMS_* (1..3)");
-        if (s->s.encode_only) throw kbhip::Error(KBHIP_EINVAL, "encode-only session has no device state");
-        kbhip::require_no_tickets(s->s);
-        HIPCHK(hipSetDevice(s->s.device));
-        return kbhip::rank_victim_nodes_abi(s->s, task_id, by_score != 0, victims, first, out_node, out_score,
-                                            out_cands, cap, out_info);
+        return kbhip::rank_victim_nodes_abi(kbhip::device_session(s), task_id, by_score != 0, victims, first, out_node,
+                                            out_score, out_cands, cap, out_info);
     })
 }
 

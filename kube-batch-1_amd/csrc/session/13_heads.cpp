@@ -9,14 +9,6 @@ static_assert(KBHIP_RANK_HEADS_MAX == kMaxChunk, "one PopCtrl task slot per requ
 
 constexpr size_t align8(size_t x) { return (x + 7) & ~(size_t)7; }
 
-void pinned_fit(Session& S, void** p, size_t* cap, size_t bytes) {
-    if (*p && *cap >= bytes) return;
-    if (*p) MemPool::get().give(MemPool::kPinned, *p, *cap, S.device);
-    *p = nullptr;
-    *cap = 0;
-    *p = MemPool::get().take(MemPool::kPinned, bytes, cap);
-}
-
 }  // namespace
 
 // The heads (entries [0, cap) of the walk order and the order's length) of
@@ -35,18 +27,9 @@ void pinned_fit(Session& S, void** p, size_t* cap, size_t bytes) {
 int64_t rank_heads_abi(Session& S, const int32_t* task_ids, int n, bool by_score, int mode, int cap,
                        int64_t* out_total, int32_t* out_node, int32_t* out_score, int32_t* out_cands,
                        int64_t* out_info) {
-    for (int i = 0; i < n; ++i) {
-        const int pod = task_ids[i];
-        const string at = "kbhip_rank_heads: task_ids[" + std::to_string(i) + "] ";
-        if (pod < 0 || pod >= (int)S.pods.size() || S.pods[pod].cls < 0)
-            throw Error(KBHIP_EINVAL, at + "has no task class (not a pending task of the session)");
-        if (S.pods[pod].status != Pending) throw Error(KBHIP_EINVAL, at + "is not Pending (the session placed it)");
-        const int jb = S.pods[pod].job;
-        if (mode != 0 && (jb < 0 || S.jobs[jb].queue < 0 || S.jobs[jb].queue >= (int)S.queues.size()))
-            throw Error(KBHIP_EINVAL, at + "has no job");
-    }
-    if (S.world != 1) throw Error(KBHIP_EUNSUPPORTED, "kbhip_rank_heads on a node-sharded session");
-    ov_quiesce(S);
+    for (int i = 0; i < n; ++i)
+        query_task(S, task_ids[i], "kbhip_rank_heads: task_ids[" + std::to_string(i) + "] ", mode != 0);
+    query_begin(S, "kbhip_rank_heads");
     const bool rebuilt = mode != 0 && vict_ensure(S);
 
     // the distinct jobs' own lists, to be concatenated (off: in list entries): job_of[i] = request i's entry of owns
@@ -75,29 +58,26 @@ int64_t rank_heads_abi(Session& S, const int32_t* task_ids, int n, bool by_score
     const size_t off_desc = align8(sizeof(PopCtrl)), off_sum = align8(off_desc + (size_t)n * sizeof(HeadDesc)),
                  off_node = off_sum + own_total * 4 * sizeof(int64_t),
                  in_bytes = align8(off_node + own_total * sizeof(int32_t));
-    pinned_fit(S, (void**)&S.h_heads_in, &S.h_heads_in_cap, std::max<size_t>(2 * in_bytes, 1 << 16));
-    pinned_fit(S, (void**)&S.h_heads_out, &S.h_heads_out_cap, (size_t)kMaxChunk * (kTopK + 1) * sizeof(uint64_t));
-    if (!S.b_heads_in.p || S.heads_in_cap < in_bytes) {
-        HIPCHK(hipStreamSynchronize(S.stream));
-        S.heads_in_cap = std::max<size_t>(2 * in_bytes, 1 << 16);
-        S.b_heads_in.alloc<uint8_t>(S.heads_in_cap);
-    }
+    S.h_heads_in.fit(in_bytes, std::max<size_t>(2 * in_bytes, 1 << 16));
+    S.h_heads_out.fit((size_t)kMaxChunk * (kTopK + 1) * sizeof(uint64_t));
+    S.b_heads_in.grow(S.stream, in_bytes, std::max<size_t>(2 * in_bytes, 1 << 16));
     if (!S.b_heads.p) S.b_heads.alloc<uint64_t>(rank_heads_words());
 
+    uint8_t* const h_in = S.h_heads_in.as<uint8_t>();
     uint8_t* const d_in = (uint8_t*)S.b_heads_in.p;
-    PopCtrl* const h_ctrl = (PopCtrl*)S.h_heads_in;
+    PopCtrl* const h_ctrl = (PopCtrl*)h_in;
     PopCtrl* const d_ctrl = (PopCtrl*)d_in;
-    HeadDesc* const h_desc = (HeadDesc*)(S.h_heads_in + off_desc);
-    std::memset(S.h_heads_in, 0, off_sum);
+    HeadDesc* const h_desc = (HeadDesc*)(h_in + off_desc);
+    std::memset(h_in, 0, off_sum);
     h_ctrl->stop = -1;
     h_ctrl->n_tasks = n;
     h_ctrl->any_bf = S.any_bf;
     h_ctrl->fallback = S.fallback;
     for (const Own& o : owns) {
         if (o.node.empty()) continue;
-        std::memcpy(S.h_heads_in + off_sum + o.off * 4 * sizeof(int64_t), o.sum.data(),
+        std::memcpy(h_in + off_sum + o.off * 4 * sizeof(int64_t), o.sum.data(),
                     o.node.size() * 4 * sizeof(int64_t));
-        std::memcpy(S.h_heads_in + off_node + o.off * sizeof(int32_t), o.node.data(), o.node.size() * sizeof(int32_t));
+        std::memcpy(h_in + off_node + o.off * sizeof(int32_t), o.node.data(), o.node.size() * sizeof(int32_t));
     }
     int ipa_slots[kMaxChunk], n_ipa = 0;
     for (int i = 0; i < n; ++i) {
@@ -124,18 +104,18 @@ int64_t rank_heads_abi(Session& S, const int32_t* task_ids, int n, bool by_score
     }
 
     int64_t launches = flush_tables(S);  // evictions / unevicts so far change pod-affinity predicates
-    HIPCHK(hipMemcpyAsync(d_in, S.h_heads_in, in_bytes, hipMemcpyHostToDevice, S.stream));
+    HIPCHK(hipMemcpyAsync(d_in, h_in, in_bytes, hipMemcpyHostToDevice, S.stream));
     for (int k = 0; k < n_ipa; ++k) HIPCHK(launch_ipa_minmax(S.nc, S.tab, d_ctrl, ipa_slots[k], S.stream));
     int bx = 0;
     HIPCHK(launch_rank_heads(S.conf, S.nc, S.tab, (const HeadDesc*)(d_in + off_desc), n, mode != 0, d_ctrl,
                              by_score ? 1 : 0, (uint64_t*)S.b_heads.p, &bx, S.stream));
-    HIPCHK(hipMemcpyAsync(S.h_heads_out, S.b_heads.p, (size_t)n * (kTopK + 1) * sizeof(uint64_t),
+    HIPCHK(hipMemcpyAsync(S.h_heads_out.p, S.b_heads.p, (size_t)n * (kTopK + 1) * sizeof(uint64_t),
                           hipMemcpyDeviceToHost, S.stream));
     HIPCHK(hipStreamSynchronize(S.stream));
     launches += n_ipa + 2;
 
     for (int i = 0; i < n; ++i) {
-        const uint64_t* keys = S.h_heads_out + (size_t)i * (kTopK + 1);
+        const uint64_t* keys = S.h_heads_out.as<uint64_t>() + (size_t)i * (kTopK + 1);
         const int64_t total = (int64_t)keys[kTopK], n_keys = std::min<int64_t>(cap, total);
         const size_t row = (size_t)i * cap;
         const Own* o = job_of[i] >= 0 ? &owns[job_of[i]] : nullptr;
@@ -174,7 +154,6 @@ int64_t kbhip_rank_heads(kb_session* s, const int32_t* task_ids, int32_t n_tasks
                          int32_t cap, int64_t* out_total, int32_t* out_node, int32_t* out_score, int32_t* out_cands,
                          int64_t* out_info) {
     ABI_GUARD_S(s, {
-        if (!s) throw kbhip::Error(KBHIP_EINVAL, "null session");
         if (n_tasks < 0 || n_tasks > KBHIP_RANK_HEADS_MAX)
             throw kbhip::Error(KBHIP_EINVAL, "kbhip_rank_heads: n_tasks is 0 .. KBHIP_RANK_HEADS_MAX (64)");
         if (cap < 1 || cap > 64) throw kbhip::Error(KBHIP_EINVAL, "kbhip_rank_heads: cap is 1 .. 64");
@@ -183,11 +162,9 @@ int64_t kbhip_rank_heads(kb_session* s, const int32_t* task_ids, int32_t n_tasks
             throw kbhip::Error(KBHIP_EINVAL, "kbhip_rank_heads: victims is 0 or one of KBHIP_VICTIMS_* (1..3)");
         if (!task_ids || !out_total || !out_node)
             throw kbhip::Error(KBHIP_EINVAL, "kbhip_rank_heads: null task_ids, out_total or out_node");
-        if (s->s.encode_only) throw kbhip::Error(KBHIP_EINVAL, "encode-only session has no device state");
-        kbhip::require_no_tickets(s->s);
+        kbhip::Session& S = kbhip::device_session(s);
         if (n_tasks == 0) return 0;
-        HIPCHK(hipSetDevice(s->s.device));
-        return kbhip::rank_heads_abi(s->s, task_ids, n_tasks, by_score != 0, victims, cap, out_total, out_node,
+        return kbhip::rank_heads_abi(S, task_ids, n_tasks, by_score != 0, victims, cap, out_total, out_node,
                                      out_score, out_cands, out_info);
     })
 }

@@ -15,18 +15,6 @@ static_assert(KBHIP_WHY_SHORT_CPU == (2 << kWhyShortShift) && KBHIP_WHY_SHORT_ME
                   KBHIP_WHY_SHORT_GPU == (8 << kWhyShortShift),
               "the short bits are fit_bits' bits 1..3");
 
-namespace {
-
-void pinned_fit(Session& S, void** p, size_t* cap, size_t bytes) {
-    if (*p && *cap >= bytes) return;
-    if (*p) MemPool::get().give(MemPool::kPinned, *p, *cap, S.device);
-    *p = nullptr;
-    *cap = 0;
-    *p = MemPool::get().take(MemPool::kPinned, bytes, cap);
-}
-
-}  // namespace
-
 // The verdicts and histograms of n tasks of the session as it stands: the
 // tasks' classes go up in one copy from pinned staging, one sweep launch and
 // one reduce launch follow, then one copy of the n histograms (and, when asked
@@ -34,47 +22,33 @@ void pinned_fit(Session& S, void** p, size_t* cap, size_t bytes) {
 // changes nothing: no node row, no visit counter, not fit_task.
 int64_t explain_tasks_abi(Session& S, const int32_t* task_ids, int n, uint8_t* out_verdict, int64_t* out_hist,
                           int64_t* out_info) {
-    for (int i = 0; i < n; ++i) {
-        const int pod = task_ids[i];
-        const string at = "kbhip_explain_tasks: task_ids[" + std::to_string(i) + "] ";
-        if (pod < 0 || pod >= (int)S.pods.size() || S.pods[pod].cls < 0)
-            throw Error(KBHIP_EINVAL, at + "has no task class (not a pending task of the session)");
-        if (S.pods[pod].status != Pending) throw Error(KBHIP_EINVAL, at + "is not Pending (the session placed it)");
-    }
-    if (S.world != 1) throw Error(KBHIP_EUNSUPPORTED, "kbhip_explain_tasks on a node-sharded session");
-    ov_quiesce(S);
+    for (int i = 0; i < n; ++i)
+        query_task(S, task_ids[i], "kbhip_explain_tasks: task_ids[" + std::to_string(i) + "] ", false);
+    query_begin(S, "kbhip_explain_tasks");
 
     const int N = S.nc.n;
     const int bx = explain_bx(N, n, S.explain_blocks);
     const size_t in_bytes = (size_t)n * sizeof(TaskClass);
     const size_t part_words = (size_t)n * bx * kWhyBins, out_bytes = (size_t)n * kWhyBins * sizeof(int64_t);
     const size_t v_bytes = out_verdict ? (size_t)n * (size_t)N : 0;
-    pinned_fit(S, (void**)&S.h_explain_in, &S.h_explain_in_cap, (size_t)kMaxChunk * sizeof(TaskClass));
-    pinned_fit(S, (void**)&S.h_explain_out, &S.h_explain_out_cap, (size_t)kMaxChunk * kWhyBins * sizeof(int64_t));
+    S.h_explain_in.fit((size_t)kMaxChunk * sizeof(TaskClass));
+    S.h_explain_out.fit((size_t)kMaxChunk * kWhyBins * sizeof(int64_t));
     if (!S.b_explain_in.p) S.b_explain_in.alloc<TaskClass>(kMaxChunk);
     if (!S.b_explain_out.p) S.b_explain_out.alloc<int64_t>((size_t)kMaxChunk * kWhyBins);
-    if (!S.b_explain_part.p || S.explain_part_words < part_words) {
-        HIPCHK(hipStreamSynchronize(S.stream));
-        S.b_explain_part.alloc<uint32_t>(part_words);
-        S.explain_part_words = part_words;
-    }
-    if (v_bytes && (!S.b_explain_v.p || S.explain_v_bytes < v_bytes)) {
-        HIPCHK(hipStreamSynchronize(S.stream));
-        S.b_explain_v.alloc<uint8_t>(v_bytes);
-        S.explain_v_bytes = v_bytes;
-    }
-    for (int i = 0; i < n; ++i) S.h_explain_in[i] = S.classes[S.pods[task_ids[i]].cls];
+    S.b_explain_part.grow(S.stream, part_words * sizeof(uint32_t), part_words * sizeof(uint32_t));
+    if (v_bytes) S.b_explain_v.grow(S.stream, v_bytes, v_bytes);
+    for (int i = 0; i < n; ++i) S.h_explain_in.as<TaskClass>()[i] = S.classes[S.pods[task_ids[i]].cls];
 
     int64_t launches = flush_tables(S);  // evictions / unevicts so far change pod-affinity predicates
-    HIPCHK(hipMemcpyAsync(S.b_explain_in.p, S.h_explain_in, in_bytes, hipMemcpyHostToDevice, S.stream));
+    HIPCHK(hipMemcpyAsync(S.b_explain_in.p, S.h_explain_in.p, in_bytes, hipMemcpyHostToDevice, S.stream));
     HIPCHK(launch_explain(S.conf, S.nc, S.tab, (const TaskClass*)S.b_explain_in.p, n, bx,
                           v_bytes ? (uint8_t*)S.b_explain_v.p : nullptr, (uint32_t*)S.b_explain_part.p,
                           (int64_t*)S.b_explain_out.p, S.stream));
     launches += 2;
-    HIPCHK(hipMemcpyAsync(S.h_explain_out, S.b_explain_out.p, out_bytes, hipMemcpyDeviceToHost, S.stream));
+    HIPCHK(hipMemcpyAsync(S.h_explain_out.p, S.b_explain_out.p, out_bytes, hipMemcpyDeviceToHost, S.stream));
     if (v_bytes) HIPCHK(hipMemcpyAsync(out_verdict, S.b_explain_v.p, v_bytes, hipMemcpyDeviceToHost, S.stream));
     HIPCHK(hipStreamSynchronize(S.stream));
-    std::memcpy(out_hist, S.h_explain_out, out_bytes);
+    std::memcpy(out_hist, S.h_explain_out.p, out_bytes);
     if (out_info) {
         out_info[0] = launches;
         out_info[1] = bx;
@@ -109,16 +83,13 @@ extern "C" {
 int64_t kbhip_explain_tasks(kb_session* s, const int32_t* task_ids, int32_t n_tasks, uint8_t* out_verdict,
                             int64_t* out_hist, int64_t* out_info) {
     ABI_GUARD_S(s, {
-        if (!s) throw kbhip::Error(KBHIP_EINVAL, "null session");
         if (n_tasks < 0 || n_tasks > KBHIP_EXPLAIN_MAX)
             throw kbhip::Error(KBHIP_EINVAL, "kbhip_explain_tasks: n_tasks is 0 .. KBHIP_EXPLAIN_MAX (64)");
         if (n_tasks > 0 && (!task_ids || !out_hist))
             throw kbhip::Error(KBHIP_EINVAL, "kbhip_explain_tasks: null task_ids or out_hist");
-        if (s->s.encode_only) throw kbhip::Error(KBHIP_EINVAL, "encode-only session has no device state");
-        kbhip::require_no_tickets(s->s);
+        kbhip::Session& S = kbhip::device_session(s);
         if (n_tasks == 0) return 0;
-        HIPCHK(hipSetDevice(s->s.device));
-        return kbhip::explain_tasks_abi(s->s, task_ids, n_tasks, out_verdict, out_hist, out_info);
+        return kbhip::explain_tasks_abi(S, task_ids, n_tasks, out_verdict, out_hist, out_info);
     })
 }
 

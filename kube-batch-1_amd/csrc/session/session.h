@@ -9,9 +9,12 @@
 // action and its speculation, first_fit), 05_actions (backfill, the standalone
 // sweeps, the actions' C-ABI entry points), 06_carry (session carry-over),
 // 07_abi (the remaining C-ABI entry points), 08_walk (the walk read-outs),
-// 09_rank (kbhip_rank_nodes), 10_ops (kbhip_apply_ops), 11_evict (the reclaim /
-// preempt actions and the device ranking of a task's nodes), 12_victims (the
-// victim-candidate table and kbhip_rank_victim_nodes).  framework.h, which
+// 09_query (the prologue the task queries share), 10_ops (kbhip_apply_ops),
+// 11_evict (the reclaim / preempt actions and the device ranking of a task's
+// nodes), 12_rank (the walk window of one task: kbhip_rank_nodes,
+// kbhip_rank_victim_nodes and the victim-candidate table), 13_heads
+// (kbhip_rank_heads), 14_explain (kbhip_explain_tasks).  buffers.h holds DevBuf
+// and PinnedBuf, the holders of pooled device and pinned memory.  framework.h, which
 // the parts running actions include, is the C++ mirror of the Go framework they
 // share: the heaps, the ordering plugins, the status index, the statements.
 //
@@ -477,31 +480,9 @@ struct SpareVec {
     }
 };
 
-struct DevBuf {  // device memory (pooled), or host memory for encode-only sessions
-    void* p = nullptr;
-    bool host = false;
-    size_t cap = 0;
-    int dev = 0;
-    ~DevBuf() { release(); }
-    void release() {
-        if (p) { if (host) std::free(p); else MemPool::get().give(MemPool::kDevice, p, cap, dev); }
-        p = nullptr;
-    }
-    template <typename T>
-    T* alloc(size_t n, bool on_host = false) {
-        release();
-        host = on_host;
-        size_t bytes = std::max<size_t>(n * sizeof(T), 16);
-        if (host) {
-            p = std::calloc(1, bytes);
-            if (!p) throw Error(KBHIP_EINVAL, "out of host memory");
-        } else {
-            (void)hipGetDevice(&dev);
-            p = MemPool::get().take(MemPool::kDevice, bytes, &cap);
-        }
-        return (T*)p;
-    }
-};
+}  // namespace kbhip
+#include "buffers.h"  // DevBuf, PinnedBuf: the holders of pooled device and pinned memory
+namespace kbhip {
 
 inline SpareVec<HPod>& spare_pods() {
     static SpareVec<HPod> sp;
@@ -593,11 +574,9 @@ struct Session {
     DevBuf b_tab_idx;  // count-table deltas (flush_tables)
     DevBuf b_sweep_cnt;  // kbhip_sweep_scores' passing counts (8 counters, one 128-B line each)
     DevBuf b_rank_head;  // kbhip_rank_nodes' head path: result, block lists, block counts (rank_head_words)
-    uint64_t* h_rank_head = nullptr;  // pinned: its kTopK keys, then the passing count
-    size_t h_rank_head_cap = 0;
+    PinnedBuf h_rank_head;  // uint64_t: its kTopK keys, then the passing count
     size_t rank_tmp_bytes = 0;
-    uint64_t* h_rank = nullptr;  // pinned: [0] = count, then sorted keys
-    size_t h_rank_cap = 0;
+    PinnedBuf h_rank;  // uint64_t: [0] = count, then sorted keys
     int rank_first = 2048;  // sorted keys read back with the count (option "rank_first"); the rest on demand
     bool force_radix = false;  // option "rank_radix": the wide-range radix passes for every class (tests)
     bool bf_batch = true;      // option "bf_batch": batched pops (placement 6) in sessions with Backfilled nodes
@@ -618,48 +597,34 @@ struct Session {
     // model_gen; a carry-over ends both); ops_sim[pod] = the pod's status as the batch under validation
     // left it (-1 between calls).
     DevBuf b_ops;
-    size_t b_ops_bytes = 0;
-    uint8_t* h_ops = nullptr;  // pinned
-    size_t h_ops_cap = 0;
+    PinnedBuf h_ops;
     hipEvent_t ev_ops = nullptr;
     vector<int32_t> ops_seg;
     vector<int32_t> ops_sim;
     vector<uint8_t> op_mark;
     uint64_t op_mark_gen = ~0ull;
-    // kbhip_rank_victim_nodes (12_victims.cpp): the victim-candidate table [Q + 1][4][npad] (VictArgs,
+    // kbhip_rank_victim_nodes (12_rank.cpp): the victim-candidate table [Q + 1][4][npad] (VictArgs,
     // kbhip_internal.h) on the host and the device.  vict_live: both are current — built by the first ranking
     // that needs it, kept current by kbhip_apply_ops, cleared by every other call that changes pod statuses
     // (vict_stale below) and rebuilt by the next ranking.  b_vict_own / h_vict_own: the job's own list of one
     // call (sums, then nodes); b_vict_blk / b_vict_keys / b_vict_cands: the full path's compaction;
-    // h_vict_out: pinned, [0] = the kept count, then the window's candidate counts.
+    // h_vict_out: int32_t, [0] = the kept count, then the window's candidate counts.
     vector<int64_t> vict_tab;
     bool vict_live = false;
     DevBuf b_vict, b_vict_own, b_vict_blk, b_vict_keys, b_vict_cands;
-    size_t vict_own_cap = 0;
-    uint8_t* h_vict_own = nullptr;
-    size_t h_vict_own_cap = 0;
-    int32_t* h_vict_out = nullptr;
-    size_t h_vict_out_cap = 0;
-    // kbhip_rank_heads (13_heads.cpp).  h_heads_in (pinned) / b_heads_in: one call's upload — a PopCtrl image
+    PinnedBuf h_vict_own, h_vict_out;
+    // kbhip_rank_heads (13_heads.cpp).  h_heads_in / b_heads_in: one call's upload — a PopCtrl image
     // of the call's own (slot i: request i's class, inter-pod min / max zero), its HeadDescs, the own-job
-    // lists of its jobs; b_heads: the kernels' scratch (rank_heads_words); h_heads_out (pinned): kMaxChunk
+    // lists of its jobs; b_heads: the kernels' scratch (rank_heads_words); h_heads_out: kMaxChunk
     // results of kTopK keys and the count.
     DevBuf b_heads_in, b_heads;
-    size_t heads_in_cap = 0;
-    uint8_t* h_heads_in = nullptr;
-    size_t h_heads_in_cap = 0;
-    uint64_t* h_heads_out = nullptr;
-    size_t h_heads_out_cap = 0;
-    // kbhip_explain_tasks (14_explain.cpp).  h_explain_in (pinned) / b_explain_in: one call's task classes;
-    // b_explain_part: the sweep's block counts [request][block][16]; b_explain_out / h_explain_out (pinned):
+    PinnedBuf h_heads_in, h_heads_out;
+    // kbhip_explain_tasks (14_explain.cpp).  h_explain_in / b_explain_in: one call's task classes;
+    // b_explain_part: the sweep's block counts [request][block][16]; b_explain_out / h_explain_out:
     // the histograms; b_explain_v: the verdict rows of a call that asks for them.  explain_blocks: option
     // "explain_blocks" (tests; 0 = automatic): the sweep's grid x is at most this.
     DevBuf b_explain_in, b_explain_part, b_explain_out, b_explain_v;
-    size_t explain_part_words = 0, explain_v_bytes = 0;
-    TaskClass* h_explain_in = nullptr;
-    size_t h_explain_in_cap = 0;
-    int64_t* h_explain_out = nullptr;
-    size_t h_explain_out_cap = 0;
+    PinnedBuf h_explain_in, h_explain_out;
     int explain_blocks = 0;
     int32_t fallback = -1;  // lowest node index holding a session-placed pod (nodeorder.go:78-93)
     vector<int32_t> sess_cnt;  // per node: session-placed pods on it (fallback after an unpipeline)
@@ -879,33 +844,11 @@ struct Session {
         b_eng_tl.release();
         d_eng_tl = nullptr;
         eng_nw = 0;
-        if (h_rank) MemPool::get().give(MemPool::kPinned, h_rank, h_rank_cap, device);
-        h_rank = nullptr;
-        if (h_rank_head) MemPool::get().give(MemPool::kPinned, h_rank_head, h_rank_head_cap, device);
-        h_rank_head = nullptr;
-        if (h_ops) MemPool::get().give(MemPool::kPinned, h_ops, h_ops_cap, device);
-        h_ops = nullptr;
+        for (PinnedBuf* b : {&h_rank, &h_rank_head, &h_ops, &h_vict_own, &h_vict_out, &h_heads_in, &h_heads_out,
+                             &h_explain_in, &h_explain_out})
+            b->release();
         if (ev_ops) { (void)hipEventDestroy(ev_ops); ev_ops = nullptr; }
-        b_ops.release();
-        if (h_vict_own) MemPool::get().give(MemPool::kPinned, h_vict_own, h_vict_own_cap, device);
-        h_vict_own = nullptr;
-        if (h_vict_out) MemPool::get().give(MemPool::kPinned, h_vict_out, h_vict_out_cap, device);
-        h_vict_out = nullptr;
-        for (DevBuf* b : {&b_vict, &b_vict_own, &b_vict_blk, &b_vict_keys, &b_vict_cands}) b->release();
         vict_live = false;
-        if (h_heads_in) MemPool::get().give(MemPool::kPinned, h_heads_in, h_heads_in_cap, device);
-        h_heads_in = nullptr;
-        if (h_heads_out) MemPool::get().give(MemPool::kPinned, h_heads_out, h_heads_out_cap, device);
-        h_heads_out = nullptr;
-        b_heads_in.release();
-        b_heads.release();
-        heads_in_cap = 0;
-        if (h_explain_in) MemPool::get().give(MemPool::kPinned, h_explain_in, h_explain_in_cap, device);
-        h_explain_in = nullptr;
-        if (h_explain_out) MemPool::get().give(MemPool::kPinned, h_explain_out, h_explain_out_cap, device);
-        h_explain_out = nullptr;
-        for (DevBuf* b : {&b_explain_in, &b_explain_part, &b_explain_out, &b_explain_v}) b->release();
-        explain_part_words = explain_v_bytes = 0;
         h_out = nullptr;
         if (cu_masked) {  // streams of option "cu_split" are this session's own
             for (int k = 1; k <= kMaxDep; ++k)
@@ -921,7 +864,9 @@ struct Session {
         for (DevBuf* b : {&b_labels, &b_taints, &b_ports, &b_classes, &b_terms, &b_reqs, &b_vals, &b_valint, &b_valok,
                           &b_masks, &b_ctrl, &b_walk, &b_dom, &b_aff_items, &b_aff_cnt, &b_aff_scalar, &b_cand2,
                           &b_arrive, &b_link, &b_dbg, &b_fit4, &b_rank_keys, &b_rank_sorted, &b_rank_tmp, &b_rank_cnt,
-                          &b_rank_radix, &b_rank_head,
+                          &b_rank_radix, &b_rank_head, &b_ops, &b_vict, &b_vict_own, &b_vict_blk, &b_vict_keys,
+                          &b_vict_cands, &b_heads_in, &b_heads, &b_explain_in, &b_explain_part, &b_explain_out,
+                          &b_explain_v,
                           &b_shard_send, &b_shard_recv, &b_tab_idx, &b_sweep_cnt, &b_dd_max, &b_cmp_mask, &b_cmp_blk,
                           &b_cmp_node, &b_cmp_val})
             b->release();
@@ -1229,11 +1174,9 @@ void sweep_chunk(Session& S, int m, const int* cls, bool defer, bool per_task = 
 int take_slot(Session& S, uint32_t* epoch);
 void sweep_task(Session& S, int i, int cls, bool defer_visits = false);
 void rank_buffers(Session& S);
-void rank_launch(Session& S, int cls, bool by_score);
+int rank_launch(Session& S, int cls, bool by_score);  // the kernel launches it made
 void backfill_run(Session& S);
 int sweep_scores(Session& S, int pod, uint64_t* out_keys);
-int64_t rank_nodes_abi(Session& S, int pod, bool by_score, int64_t first, int32_t* out_node, int32_t* out_score,
-                       int64_t cap);
 int64_t walk_visits(Session& S, int32_t* out_node, uint32_t* out_count, int64_t cap);
 int64_t fit_deltas(Session& S, int pod, int32_t* out_node, int64_t* out_delta, int64_t cap);
 double time_sweeps(Session& S, const int32_t* ids, int n);
@@ -1257,7 +1200,18 @@ struct NodeOp {
     R3 req;
     int32_t queue = -1;  // an eviction: the pod's job's queue (the victim-candidate table's row)
 };
-// kbhip_rank_victim_nodes (12_victims.cpp).  vict_stale: the call that follows changes pod statuses outside
+// Task queries (kbhip_rank_nodes, kbhip_rank_victim_nodes, kbhip_rank_heads, kbhip_explain_tasks: calls that
+// read the session as it stands for pending tasks and change nothing in it) open alike (09_query.cpp).
+// query_task: task id `pod` checked — it has a task class, it is Pending and, with need_job, its job has a
+// queue; the error texts start with `prefix` ("kbhip_x: task_ids[i] " for the batched calls; the single-task
+// calls pass "kbhip_x: the task " and, for the no-class text, no_class_prefix "task id ").  query_begin,
+// once every task passed: node-sharded sessions refused, the overlapped pops drained (ov_quiesce).  A new
+// query calls the two, takes its staging from PinnedBuf::fit and DevBuf::grow, and flush_tables before its
+// first launch.
+const HPod& query_task(const Session& S, int pod, const string& prefix, bool need_job,
+                       const char* no_class_prefix = nullptr);
+void query_begin(Session& S, const char* api_name);
+// kbhip_rank_victim_nodes (12_rank.cpp).  vict_stale: the call that follows changes pod statuses outside
 // kbhip_apply_ops — the victim-candidate table is rebuilt by the next ranking that needs it.
 inline void vict_stale(Session& S) { S.vict_live = false; }
 // A candidate victim: Running with a Running copy on its node, and a job (EvictAction::build_node_tasks' run_copy).
@@ -1266,6 +1220,7 @@ inline bool vict_candidate(const Session& S, const HPod& p) {
 }
 // a batch of kbhip_apply_ops on the host copy of a live table (the device copy: launch_apply_ops)
 void vict_apply_evictions(Session& S, const vector<NodeOp>& ops);
+// mode 0: kbhip_rank_nodes (no victim test; out_cands and out_info null)
 int64_t rank_victim_nodes_abi(Session& S, int pod, bool by_score, int mode, int64_t first, int32_t* out_node,
                               int32_t* out_score, int32_t* out_cands, int64_t cap, int64_t* out_info);
 // The parts of that call kbhip_rank_heads (13_heads.cpp) shares.  vict_ensure: the table built unless it is
@@ -1307,6 +1262,18 @@ inline void taint_comm(kb_session* s) {
 inline void check_usable(kb_session* s) {
     if (s && !s->s.broken.empty()) throw kbhip::Error(KBHIP_EINVAL, s->s.broken);
 }
+
+// The preamble of an ABI call that runs device work on a session, after the call's own argument checks:
+// the session exists, has device state and no job pops outstanding; its device is the current one.
+namespace kbhip {
+inline Session& device_session(kb_session* s) {
+    if (!s) throw Error(KBHIP_EINVAL, "null session");
+    if (s->s.encode_only) throw Error(KBHIP_EINVAL, "encode-only session has no device state");
+    require_no_tickets(s->s);
+    HIPCHK(hipSetDevice(s->s.device));
+    return s->s;
+}
+}  // namespace kbhip
 
 inline void check_log_args(kb_session* s, const int32_t* out_pod, const int32_t* out_node, const uint8_t* out_kind,
                            int64_t cap) {
