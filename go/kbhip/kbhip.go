@@ -361,6 +361,73 @@ func (e *Engine) RankHeads(tasks []int32, byScore bool, victims int32, cap int) 
 	return heads, info, nil
 }
 
+// The flag bits of a HeadVictim (KBHIP_HEAD_VICTIMS_*).
+const (
+	HeadVictimsValid  = uint8(C.KBHIP_HEAD_VICTIMS_VALID)
+	HeadVictimsCovers = uint8(C.KBHIP_HEAD_VICTIMS_COVERS)
+)
+
+// HeadVictim is one head node of HeadVictims: what ssn.Reclaimable /
+// ssn.Preemptable answer on it (Count victims, the first min(Count, stride) of
+// them in Victims), whether validateVictims passes (Flags & HeadVictimsValid),
+// how many victims from the front the eviction loop evicts (Evict) and whether
+// it then pipelines the task here (Flags & HeadVictimsCovers).
+type HeadVictim struct {
+	Node, Score  int32
+	Count, Evict int32
+	Flags        uint8
+	Victims      []int32
+}
+
+// HeadVictimsInfo says what a HeadVictims call did (out_info of kbhip_head_victims).
+type HeadVictimsInfo struct {
+	Rebuilt      bool  // the candidate table was built by this call
+	StateRebuilt bool  // the victim state was built by this call
+	Patched      int64 // records of earlier ApplyOps batches patched into it
+	Launches     int64 // kernel launches issued
+	MaxCount     int64 // the largest Count: a stride below it truncated a row
+}
+
+// HeadVictims answers the head of RankVictimNodes' walk together with the
+// victim decision on each head node (kbhip_head_victims): the step of a
+// reclaim / preempt loop between the ranking and ApplyOps.  1 <= cap <= 64,
+// stride >= 1.  The rows describe the session at the call: use them up to the
+// first node acted on and discard the rest once an ApplyOps is sent.
+func (e *Engine) HeadVictims(task int32, byScore bool, victims int32, cap, stride int) (total int64, heads []HeadVictim, info HeadVictimsInfo, err error) {
+	if cap < 1 || cap > 64 || stride < 1 { // (also keeps &x[0] below off empty slices)
+		return 0, nil, info, fmt.Errorf("kbhip head_victims: cap %d (1..64), stride %d (>= 1)", cap, stride)
+	}
+	nodes, scores := make([]int32, cap), make([]int32, cap)
+	counts, evicts := make([]int32, cap), make([]int32, cap)
+	flags := make([]uint8, cap)
+	rows := make([]int32, cap*stride)
+	var raw [5]C.int64_t
+	t := C.kbhip_head_victims(e.s, C.int32_t(task), boolI32(byScore), C.int32_t(victims), C.int32_t(cap),
+		C.int32_t(stride), (*C.int32_t)(unsafe.Pointer(&nodes[0])), (*C.int32_t)(unsafe.Pointer(&scores[0])),
+		(*C.int32_t)(unsafe.Pointer(&counts[0])), (*C.int32_t)(unsafe.Pointer(&evicts[0])),
+		(*C.uint8_t)(unsafe.Pointer(&flags[0])), (*C.int32_t)(unsafe.Pointer(&rows[0])), &raw[0])
+	if t < 0 {
+		return 0, nil, info, lastErr("head_victims", C.int(t))
+	}
+	info = HeadVictimsInfo{Rebuilt: raw[0] != 0, StateRebuilt: raw[1] != 0, Patched: int64(raw[2]),
+		Launches: int64(raw[3]), MaxCount: int64(raw[4])}
+	k := int(t)
+	if int64(t) > int64(cap) {
+		k = cap
+	}
+	heads = make([]HeadVictim, k)
+	for i := range heads {
+		n := int(counts[i])
+		if n > stride {
+			n = stride
+		}
+		lo := i * stride
+		heads[i] = HeadVictim{Node: nodes[i], Score: scores[i], Count: counts[i], Evict: evicts[i], Flags: flags[i],
+			Victims: rows[lo : lo+n : lo+n]}
+	}
+	return int64(t), heads, info, nil
+}
+
 // The verdict codes of ExplainTasks (KBHIP_WHY_*): the low four bits of a
 // verdict byte; the WhyShort* bits accompany the codes 0..2.
 const (

@@ -383,6 +383,67 @@ int64_t kbhip_rank_heads(kb_session* s, const int32_t* task_ids, int32_t n_tasks
                          int32_t victims, int32_t cap, int64_t* out_total, int32_t* out_node,
                          int32_t* out_score, int32_t* out_cands, int64_t* out_info);
 
+/* kbhip_head_victims <- the head of a task's pruned walk together with what
+ * the victim functions answer on each head node: the step of a host's reclaim
+ * / preempt loop between kbhip_rank_victim_nodes and kbhip_apply_ops.
+ * Returns the total of kbhip_rank_victim_nodes(task, by_score, victims, 0, ..,
+ * cap); out_node / out_score (optional) are exactly that call's head.  For
+ * head node i the candidates are its NodeInfo.Tasks in pod-index order that
+ * are Running with a Running node copy and a job, narrowed by `victims` as
+ * kbhip_rank_victim_nodes narrows them, and
+ *   out_count[i]   the length of the list ssn.Reclaimable (victims =
+ *                  KBHIP_VICTIMS_OTHER_QUEUES) or ssn.Preemptable (the other
+ *                  two) gives (session_plugins.go:67-148: per tier the
+ *                  intersection of the enabled plugins' answers, the first
+ *                  tier with a non-empty one decides), in candidate order
+ *   out_victim[i * stride + k]  the pod indices of that list, k <
+ *                  min(count, stride); -1 beyond
+ *   out_flags[i]   KBHIP_HEAD_VICTIMS_VALID: the count is > 0 and the
+ *                  victims' Resreq sum is not Less than the task's InitResreq
+ *                  (validateVictims, preempt.go:355-370);
+ *                  KBHIP_HEAD_VICTIMS_COVERS (with VALID only): InitResreq is
+ *                  LessEqual the evicted prefix's sum — the loop pipelines here
+ *   out_evict[i]   with VALID, how many victims from the front the loop evicts
+ *                  before it breaks (reclaim.go / preempt.go:300-320: evict,
+ *                  stop when the remaining request is LessEqual the victim's
+ *                  Resreq, else subtract and go on); 0 without VALID
+ * Rows i >= min(cap, total) are -1 (node, victims) and 0.  out_info (optional,
+ * 5 entries): whether the candidate table was rebuilt, whether the victim
+ * state was rebuilt, the records patched into it, the kernel launches, the
+ * largest out_count (a stride below it truncated a row).
+ * The answer is the one kbhip_reclaim / kbhip_preempt would compute at this
+ * moment: gang's readyTaskNum, drf's job allocations and total, proportion's
+ * allocated / deserved (the plugins are opened by the first call that needs
+ * them, as kbhip_apply_ops opens them), conformance's critical pods, and the
+ * tiers' enabled victim functions — preempt's for the two preempt modes,
+ * reclaim's for KBHIP_VICTIMS_OTHER_QUEUES.
+ * The victim state — the nodes' candidate tasks as a CSR of records in node
+ * order, one record per job and per queue — is built from the host model by
+ * the first call and kept on the device.  kbhip_apply_ops does not make it
+ * stale: it notes the pods, jobs and queues it touched, and the next call here
+ * uploads those records and applies them in one launch before its sweep (more
+ * than option "victims_dirty_max" pods waiting, default 65536: a rebuild).
+ * Every other call that changes pod statuses (the actions, kbhip_place_job and
+ * its asynchronous forms, kbhip_first_fit, the carry-overs, a kbhip_apply_ops
+ * that failed part way) leaves it stale and the next call rebuilds it.
+ * Launches: kbhip_rank_victim_nodes' head launches, then one; one copy back.
+ * The rows describe the session at the call: a host uses them up to the first
+ * node it acts on and discards the rest as soon as it sends a kbhip_apply_ops.
+ * The call changes no node row, no counter of kbhip_walk_visits, and a task
+ * kbhip_fit_deltas would answer for stays answerable.  The whole call is
+ * validated before any device work, and a refused call writes nothing.
+ * KBHIP_EINVAL: as kbhip_rank_victim_nodes, cap outside 1..64, stride < 1, a
+ * null out_node, out_count, out_evict, out_flags or out_victim.
+ * KBHIP_EUNSUPPORTED: a node-sharded session; a victim state above 512 MB (the
+ * message names the size); more than 40 victim functions and tiers. */
+#define KBHIP_HEAD_VICTIMS_VALID 1  /* validateVictims passes (preempt.go:355-370) */
+#define KBHIP_HEAD_VICTIMS_COVERS 2 /* the eviction loop's total covers InitResreq: the loop pipelines here */
+int64_t kbhip_head_victims(kb_session* s, int32_t task_id, int32_t by_score, int32_t victims /* KBHIP_VICTIMS_* */,
+                           int32_t cap /* 1..64 head nodes */, int32_t stride /* victims kept per node, >= 1 */,
+                           int32_t* out_node, int32_t* out_score /* optional */, int32_t* out_count,
+                           int32_t* out_evict, uint8_t* out_flags, int32_t* out_victim /* cap rows of stride */,
+                           int64_t* out_info /* optional */);
+
 /* kbhip_explain_tasks <- why each node is, or is not, a node of the allocate
  * walk of up to KBHIP_EXPLAIN_MAX pending tasks, on the session as it stands:
  * what the reference logs node by node (allocate.go:128-137, the error
@@ -740,6 +801,13 @@ int kbhip_shard_connect_host_gather(kb_session* s, kbhip_allgather_fn fn, void* 
  *                cpu, memory, GPU of the host tables kbhip_debug_replay mutates
  *   "node_visits"  (encode-only sessions) uint32 [n_nodes]: the walk visit
  *                counters of kbhip_walk_visits as the replay counts them
+ *   "pod_job", "pod_queue"  the session job / queue of every pod (-1: none)
+ *   "job_ready"  gang's readyTaskNum of every job; "job_drf_alloc" (double
+ *                [n_jobs][3]), "queue_allocated", "queue_deserved" (double
+ *                [n_queues][3]): drf's and proportion's state — reading one of
+ *                these four opens the plugins if no call has yet
+ *   "victim_state"  int64 [4]: kbhip_head_victims' last state build — bytes
+ *                uploaded, host microseconds, candidate tasks, longest node
  * kbhip_debug_table returns the table size in bytes and copies it when
  * cap_bytes is large enough.  Sessions from kbhip_debug_encode reject every
  * call that needs a device (KBHIP_EINVAL). */
@@ -761,6 +829,15 @@ int kbhip_debug_replay(kb_session* s, int32_t n_steps, const int32_t* pods, cons
  * that call defines them.  KBHIP_EINVAL: a null session or out_hist, a session
  * with a device, a task without a class. */
 int kbhip_debug_explain(kb_session* s, int32_t task_id, uint8_t* out_verdict, int64_t* out_hist);
+/* Test support: kbhip_head_victims' row for one node on an encode-only
+ * session's host tables, by the functions the kernel runs (vict_stage,
+ * vict_link, vict_decide, kbhip_eval.h): the count, the evicted prefix, the
+ * flags and `stride` victims as that call defines them, whether or not the
+ * node is in the task's walk.  KBHIP_EINVAL: a null session or output, a
+ * session with a device, a task without a class or a job, victims outside
+ * 1..3, a node out of range, stride < 1. */
+int kbhip_debug_victims(kb_session* s, int32_t task_id, int32_t victims, int32_t node, int32_t stride,
+                        int32_t* out_count, int32_t* out_evict, uint8_t* out_flags, int32_t* out_victim);
 
 const char* kbhip_last_error(void);
 

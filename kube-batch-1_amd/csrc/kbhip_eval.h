@@ -521,5 +521,136 @@ KBHIP_HD void after_assign(PopCtrl* ctrl, int i, int kind) {
     else if (i + 1 == ctrl->n_tasks) ctrl->stop = 0;
 }
 
+// ---------------------------------------------------------------------------
+// The victims of one node (kbhip_head_victims, kbhip_debug_victims): what
+// EvictAction::victims_of and the eviction loops of 11_evict.cpp decide, on
+// the flat records of the victim state.  Three steps, the first two
+// independent per task (a lane each on the device, a loop on the host):
+//   vict_stage   task k of the node with its job's and queue's records, and
+//                whether the call's loop would hand it to the victim functions
+//   vict_link    the first task of the node with k's job / k's queue: where
+//                the running sums of one plugin call are kept
+//   vict_decide  sequential, in task order: the plugins tier by tier, the
+//                intersection, validateVictims, the eviction prefix
+// ---------------------------------------------------------------------------
+KBHIP_HD bool vict_is_cand(const VictHdr& h, const VictTask& t, int n_jobs, int n_queues) {
+    if (!(t.flags & kVictRunCopy) || t.job < 0 || t.job >= n_jobs || t.queue >= n_queues) return false;
+    if (h.mode == 1) return t.queue >= 0 && t.queue != h.queue;             // reclaim.go: jobs of other queues
+    if (h.mode == 2) return t.queue == h.queue && t.job != h.job;           // preempt.go:104-127
+    return t.job == h.job;                                                  // preempt.go:151-181
+}
+KBHIP_HD void vict_stage(const VictState& st, const VictHdr& h, int at, VictRec& r) {
+    r.t = st.task[at];
+    r.cand = vict_is_cand(h, r.t, st.n_jobs, st.n_queues) ? 1 : 0;
+    r.alive = r.cand;
+    r.stamp = 0;
+    r.ready = 0;
+    r.jfirst = r.qfirst = 0;
+    for (int k = 0; k < 3; ++k) r.jalloc[k] = r.qalloc[k] = r.qdes[k] = r.run[k] = 0;
+    if (!r.cand) return;
+    const VictJob& j = st.job[r.t.job];
+    r.ready = j.ready;
+    for (int k = 0; k < 3; ++k) r.jalloc[k] = j.alloc[k];
+    if (r.t.queue >= 0) {
+        const VictQueue& q = st.queue[r.t.queue];
+        for (int k = 0; k < 3; ++k) { r.qalloc[k] = q.alloc[k]; r.qdes[k] = q.des[k]; }
+    }
+}
+KBHIP_HD void vict_link(VictRec* rec, int k) {
+    if (!rec[k].cand) return;
+    int jf = k, qf = k;
+    for (int i = k - 1; i >= 0; --i) {
+        if (!rec[i].cand) continue;
+        if (rec[i].t.job == rec[k].t.job) jf = i;
+        if (rec[i].t.queue == rec[k].t.queue) qf = i;
+    }
+    rec[k].jfirst = jf;
+    rec[k].qfirst = qf;
+}
+KBHIP_HD double vict_share(double l, double r) { return r == 0 ? (l == 0 ? 0 : 1) : l / r; }  // helpers.go:35-48
+KBHIP_HD double vict_drf_share(const double* a, const double* total) {  // drf.go:160-170 (Framework::drf_share_of)
+    double res = 0;
+    for (int k = 0; k < 3; ++k) { const double x = vict_share(a[k], total[k]); if (x > res) res = x; }
+    return res;
+}
+KBHIP_HD bool vict_le_f(const double* a, const double* b) {  // Resource.LessEqual (F3::less_equal)
+    return (a[0] < b[0] || fabs(b[0] - a[0]) < (double)kMinCPU) && (a[1] < b[1] || fabs(b[1] - a[1]) < (double)kMinMem) &&
+           (a[2] < b[2] || fabs(b[2] - a[2]) < (double)kMinGPU);
+}
+KBHIP_HD bool vict_le_tol(const int64_t* a, const int64_t* b) {  // EvictAction::le_tol
+    return a[0] - b[0] < kMinCPU && a[1] - b[1] < kMinMem && a[2] - b[2] < kMinGPU;
+}
+// rec[0 .. n): the node's staged tasks.  out_victim: the first min(count, stride) victims' pod indices
+// (the caller fills the rest).  Returns the victim count; *evict, *flags as kbhip.h describes them.
+KBHIP_HD int vict_decide(const VictHdr& h, VictRec* rec, int n, int stride, int32_t* out_victim, int32_t* evict,
+                         int32_t* flags) {
+    *evict = 0;
+    *flags = 0;
+    int ncand = 0;
+    for (int k = 0; k < n; ++k) ncand += rec[k].cand;
+    if (ncand == 0) return 0;  // every plugin returns nil for no candidates
+    bool init = false, decided = false;
+    int alive = 0, epoch = 0;
+    const double ls = vict_drf_share(h.la, h.total);
+    for (int ci = 0; ci < h.n_codes && !decided; ++ci) {
+        const int code = h.codes[ci];
+        if (code == 0) {  // the tier ends: the first tier with a non-empty intersection decides
+            decided = init && alive > 0;
+            continue;
+        }
+        ++epoch;
+        alive = 0;
+        for (int k = 0; k < n; ++k) {
+            VictRec& r = rec[k];
+            if (!r.cand) continue;
+            bool ans = false;
+            if (code == 1) {  // gang.go:107-129
+                ans = r.t.min_avail <= r.ready - 1 || r.t.min_avail == 1;
+            } else if (code == 2) {  // conformance.go:37-56
+                ans = !(r.t.flags & kVictCritical);
+            } else if (code == 3) {  // drf.go:84-109: every evictee of the job so far comes off, answered or not
+                VictRec& f = rec[r.jfirst];
+                if (f.stamp != epoch) { f.stamp = epoch; for (int x = 0; x < 3; ++x) f.run[x] = f.jalloc[x]; }
+                for (int x = 0; x < 3; ++x) f.run[x] -= (double)r.t.req[x];
+                const double rs = vict_drf_share(f.run, h.total);
+                ans = ls < rs || fabs(ls - rs) <= 0.000001;  // shareDelta (drf.go:29)
+            } else if (code == 4) {  // proportion.go:159-183: an evictee larger than what is left is skipped
+                VictRec& f = rec[r.qfirst];
+                if (f.stamp != epoch) { f.stamp = epoch; for (int x = 0; x < 3; ++x) f.run[x] = f.qalloc[x]; }
+                const double rq[3] = {(double)r.t.req[0], (double)r.t.req[1], (double)r.t.req[2]};
+                if (!(f.run[0] < rq[0] && f.run[1] < rq[1] && f.run[2] < rq[2])) {
+                    for (int x = 0; x < 3; ++x) f.run[x] -= rq[x];
+                    ans = vict_le_f(f.qdes, f.run);
+                }
+            }
+            if (!ans) r.alive = 0;
+            alive += r.alive;
+        }
+        init = true;
+    }
+    if (!decided) return 0;
+    // validateVictims (preempt.go:355-370), then the eviction loop (reclaim.go / preempt.go:300-320)
+    int64_t all[3] = {0, 0, 0}, got[3] = {0, 0, 0}, need[3] = {h.ireq[0], h.ireq[1], h.ireq[2]};
+    int w = 0;
+    for (int k = 0; k < n; ++k) {
+        if (!rec[k].alive) continue;
+        for (int x = 0; x < 3; ++x) all[x] += rec[k].t.req[x];
+        if (w < stride) out_victim[w] = rec[k].t.pod;
+        ++w;
+    }
+    if (all[0] < h.ireq[0] && all[1] < h.ireq[1] && all[2] < h.ireq[2]) return alive;
+    bool stop = false;
+    for (int k = 0; k < n && !stop; ++k) {
+        if (!rec[k].alive) continue;
+        const int64_t* vr = rec[k].t.req;
+        *evict += 1;
+        for (int x = 0; x < 3; ++x) got[x] += vr[x];
+        stop = vict_le_tol(need, vr);
+        for (int x = 0; x < 3; ++x) need[x] -= vr[x];
+    }
+    *flags = 1 | (vict_le_tol(h.ireq, got) ? 2 : 0);  // KBHIP_HEAD_VICTIMS_VALID, _COVERS
+    return alive;
+}
+
 
 }  // namespace kbhip

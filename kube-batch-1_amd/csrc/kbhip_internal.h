@@ -214,6 +214,71 @@ struct ApplyOps {
 // One lane per segment, as many blocks as the segments need (one launch whatever the batch holds).
 hipError_t launch_apply_ops(const NodeCols& nc, const DevTables& t, const ApplyOps& a, hipStream_t st);
 
+// kbhip_head_victims (kbhip_victims.hip): the victim state — what ssn.Reclaimable / ssn.Preemptable read
+// on a node, as flat records (device pointers; an encode-only session's host vectors for
+// kbhip_debug_victims).  task[node_off[n] .. node_off[n + 1]): the tasks of node n that were candidates
+// when the state was built (Running, a Running node copy, a job), in pod-index order — the CSR never
+// changes between rebuilds, an eviction or unevict only clears kVictRunCopy.
+constexpr int32_t kVictRunCopy = 1, kVictCritical = 2;  // VictTask::flags
+struct VictTask {
+    int32_t pod, job, queue, min_avail;
+    int64_t req[3];  // Resreq: cpu, memory, gpu
+    int32_t flags, pad;
+};
+struct VictJob {
+    double alloc[3];  // drf's allocated (HJob::drf_alloc)
+    int32_t ready, pad;  // gang's readyTaskNum
+};
+struct VictQueue {
+    double alloc[3], des[3];  // proportion's allocated / deserved
+};
+struct VictState {
+    const int32_t* node_off;  // n_nodes + 1
+    const VictTask* task;
+    const VictJob* job;
+    const VictQueue* queue;
+    int32_t n_nodes, n_jobs, n_queues, n_tasks;
+};
+// One call's constants: the task, the candidates' mode and the victim functions of the action in tier
+// order (EvictAction::compile_victims' codes: 1 gang, 2 conformance, 3 drf, 4 proportion; 0 ends a tier).
+constexpr int kVictMaxCodes = 40;
+struct VictHdr {
+    double total[3];  // drf's cluster total
+    double la[3];     // the task's job's drf allocation plus the task's Resreq (drf.go:88-90)
+    int64_t ireq[3];  // the task's InitResreq
+    int32_t mode, queue, job, n_codes;
+    int8_t codes[kVictMaxCodes];
+};
+// A node task staged for vict_decide (kbhip_eval.h): its record, its job's and queue's records, the first
+// task of the node with the same job / queue (where the running sums of one plugin call live), and the
+// decision's marks.
+struct VictRec {
+    VictTask t;
+    double jalloc[3], qalloc[3], qdes[3], run[3];
+    int32_t ready, jfirst, qfirst, stamp;
+    uint8_t cand, alive, pad[6];
+};
+constexpr int kVictLds = 256;  // node tasks a block stages in LDS; larger nodes use the spill rows
+// out_keys[0 .. kTopK] = head[0 .. kTopK] (launch_rank_head's result: the keys, then the count); row i of
+// out (3 + stride int32: count, evict, flags, then stride victims) for head entry i < cap, defined for
+// every i (entries beyond min(cap, head[kTopK]): 0 / -1).  spill: cap rows of spill_stride records, read
+// only by nodes of more than kVictLds tasks (spill_stride >= the largest node of the state).
+hipError_t launch_head_victims(const VictState& st, const VictHdr& h, const uint64_t* head, int cap, int stride,
+                               int node_base, VictRec* spill, int spill_stride, uint64_t* out_keys, int32_t* out,
+                               hipStream_t stm);
+// The records kbhip_apply_ops left dirty, scattered into the state: task[t_pos[i]].flags = t_flags[i],
+// job[j_id[i]] = j_rec[i], queue[q_id[i]] = q_rec[i] (device pointers; indices distinct within each list).
+struct VictPatch {
+    const int32_t* t_pos;
+    const int32_t* t_flags;
+    const int32_t* j_id;
+    const VictJob* j_rec;
+    const int32_t* q_id;
+    const VictQueue* q_rec;
+    int32_t n_t, n_j, n_q;
+};
+hipError_t launch_victims_patch(const VictState& st, const VictPatch& p, hipStream_t stm);
+
 // Selection-key format of a batched launch: 32-bit keys when the class's
 // score range and the node count fit (kbhip_kernels.hip, PopArgs).
 struct KeyFormat {

@@ -1,0 +1,113 @@
+// The victim sets of a walk's head nodes on gfx950 (kbhip_head_victims).
+//
+// The head sweep and merge of kbhip_heads.hip leave the best kTopK keys of a
+// task's pruned walk and their count in device memory.  k_head_victims reads
+// them there — the node list makes no host round trip — and answers, for each
+// of the first `cap` head nodes, what ssn.Reclaimable / ssn.Preemptable,
+// validateVictims and the eviction loop would decide on it, from the victim
+// state (kbhip_internal.h: the nodes' candidate tasks as a CSR of 48-byte
+// records in node order, per-job and per-queue plugin records):
+//   k_head_victims   grid cap, one wave per block, block i = head entry i.
+//                    The node's task records are consecutive: lane l loads
+//                    record l, l + 64, ... (vict_stage: the record, then its
+//                    job's and queue's records, 32 and 48 bytes gathered per
+//                    candidate) into LDS — or, for a node of more than
+//                    kVictLds tasks, into the block's spill row in device
+//                    memory — and finds the first task of its job and queue on
+//                    the node (vict_link).  Lane 0 then runs vict_decide
+//                    (kbhip_eval.h) over the staged records: the plugin chains
+//                    of drf and proportion are sequential in task order by
+//                    their definition (proportion skips an evictee without
+//                    subtracting), and the host test entry runs the same
+//                    function.  The lanes fill the victim row's tail with -1.
+//                    Block 0 also copies the head's keys and count, so that
+//                    one copy back returns everything.
+//   k_victims_patch  the records kbhip_apply_ops left dirty, one thread each.
+// Stores are plain vector stores; nothing is atomic, no block waits for another.
+#include <hip/hip_runtime.h>
+
+#include "kbhip_eval.h"
+#include "kbhip_internal.h"
+
+namespace kbhip {
+
+__global__ __launch_bounds__(64) void k_head_victims(VictState st, VictHdr h, const uint64_t* head, int cap, int stride,
+                                                     int node_base, VictRec* spill, int spill_stride,
+                                                     uint64_t* out_keys, int32_t* out) {
+    __shared__ VictRec s_rec[kVictLds];
+    const int i = blockIdx.x, lane = threadIdx.x;
+    if (i >= cap) return;
+    if (i == 0) {
+        out_keys[lane] = head[lane];
+        if (lane == 0) out_keys[kTopK] = head[kTopK];
+    }
+    int32_t* const row = out + (size_t)i * (3 + stride);
+    const uint64_t key = head[i], total = head[kTopK];
+    const int node = key_idx(key) - node_base;
+    int off = 0, n = -1;  // n < 0: no node in this row
+    if ((uint64_t)i < total && key != 0 && node >= 0 && node < st.n_nodes) {
+        off = st.node_off[node];
+        n = st.node_off[node + 1] - off;
+        if (off < 0 || n < 0 || off + n > st.n_tasks || (n > kVictLds && (!spill || n > spill_stride))) n = -1;
+    }
+    int count = 0;
+    if (n > 0) {  // (uniform over the block)
+        VictRec* const rec = n <= kVictLds ? s_rec : spill + (size_t)i * spill_stride;
+        for (int k = lane; k < n; k += 64) vict_stage(st, h, off + k, rec[k]);
+        __syncthreads();
+        for (int k = lane; k < n; k += 64) vict_link(rec, k);
+        __syncthreads();
+        if (lane == 0) {
+            int32_t evict = 0, flags = 0;
+            count = vict_decide(h, rec, n, stride, row + 3, &evict, &flags);
+            row[0] = count;
+            row[1] = evict;
+            row[2] = flags;
+        }
+        count = __shfl(count, 0, 64);
+    } else if (lane == 0) {
+        row[0] = row[1] = row[2] = 0;
+    }
+    for (int k = (count < stride ? count : stride) + lane; k < stride; k += 64) row[3 + k] = -1;
+}
+
+__global__ __launch_bounds__(256) void k_victims_patch(VictTask* task, VictJob* job, VictQueue* queue, int n_tasks,
+                                                       int n_jobs, int n_queues, VictPatch p) {
+    int i = blockIdx.x * 256 + threadIdx.x;
+    if (i < p.n_t) {
+        const int at = p.t_pos[i];
+        if (at >= 0 && at < n_tasks) task[at].flags = p.t_flags[i];
+        return;
+    }
+    i -= p.n_t;
+    if (i < p.n_j) {
+        const int j = p.j_id[i];
+        if (j >= 0 && j < n_jobs) job[j] = p.j_rec[i];
+        return;
+    }
+    i -= p.n_j;
+    if (i < p.n_q) {
+        const int q = p.q_id[i];
+        if (q >= 0 && q < n_queues) queue[q] = p.q_rec[i];
+    }
+}
+
+hipError_t launch_head_victims(const VictState& st, const VictHdr& h, const uint64_t* head, int cap, int stride,
+                               int node_base, VictRec* spill, int spill_stride, uint64_t* out_keys, int32_t* out,
+                               hipStream_t stm) {
+    if (cap < 1 || cap > kTopK || stride < 1) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_head_victims, dim3(cap), dim3(64), 0, stm, st, h, head, cap, stride, node_base, spill,
+                       spill_stride, out_keys, out);
+    return hipGetLastError();
+}
+
+hipError_t launch_victims_patch(const VictState& st, const VictPatch& p, hipStream_t stm) {
+    const int n = p.n_t + p.n_j + p.n_q;
+    if (n <= 0) return hipSuccess;
+    hipLaunchKernelGGL(k_victims_patch, dim3((n + 255) / 256), dim3(256), 0, stm, const_cast<VictTask*>(st.task),
+                       const_cast<VictJob*>(st.job), const_cast<VictQueue*>(st.queue), st.n_tasks, st.n_jobs,
+                       st.n_queues, p);
+    return hipGetLastError();
+}
+
+}  // namespace kbhip

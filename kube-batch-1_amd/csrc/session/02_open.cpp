@@ -1158,6 +1158,9 @@ void open_session(Session& S, const kbs::Snapshot& s, int device, bool encode_on
         static const vector<uint64_t> zero(kDedupMax, 0);  // (outlives the asynchronous copy)
         S.tab.dd_max = upload(S, S.b_dd_max, zero);
     }
+    // the ordering plugins' cluster total (drf.go:61-63, proportion.go:59-61); encode-only sessions too
+    // (kbhip_debug_victims)
+    for (int i = 0; i < N; ++i) S.total.add(R3{acpu[i], amem[i], agpu[i]});
     if (encode_only) {
         S.stats.nodes = N;
         S.stats.open_s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
@@ -1214,8 +1217,6 @@ void open_session(Session& S, const kbs::Snapshot& s, int device, bool encode_on
         S.keep.conf_digest = conf_digest(s);
         S.keep.node_spec_digest = node_spec_digest(s);
     }
-    // ---------------- ordering plugins OnSessionOpen ----------------
-    for (int i = 0; i < N; ++i) S.total.add(R3{acpu[i], amem[i], agpu[i]});  // drf.go:61-63, proportion.go:59-61
     mark("keep");
     S.stats.nodes = N;
     S.stats.open_s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();

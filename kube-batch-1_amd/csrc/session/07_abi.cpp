@@ -158,6 +158,10 @@ int kbhip_set_option(kb_session* s, const char* key, int64_t value) {
             if (value < 0 || value > (1 << 20)) throw kbhip::Error(KBHIP_EINVAL, "explain_blocks must be 0..2^20");
             s->s.explain_blocks = (int)value;
         }
+        else if (std::strcmp(key, "victims_dirty_max") == 0) {  // kbhip_head_victims: dirty pods patched at most
+            if (value < 0) throw kbhip::Error(KBHIP_EINVAL, "victims_dirty_max must not be negative");
+            s->s.vs_dirty_max = value;
+        }
         else if (std::strcmp(key, "bf_batch") == 0) s->s.bf_batch = value != 0;
         else if (std::strcmp(key, "aff_batch") == 0) s->s.aff_batch = value != 0;
         else if (std::strcmp(key, "aff_fence") == 0) s->s.aff_fence = value != 0;
@@ -478,8 +482,11 @@ int64_t kbhip_debug_table(kb_session* s, const char* name, void* out, int64_t ca
             for (size_t i = 0; i < S.pods.size(); ++i) v[i] = n == "pod_status" ? S.pods[i].status : S.pods[i].node;
         } else if (n == "dims") {  // n_nodes, npad, n_spaces, n_classes
             v = {S.nc.n, S.nc.npad, S.n_spaces, (int32_t)S.classes.size()};
-        } else {
-            throw kbhip::Error(KBHIP_EINVAL, "unknown table " + n);
+        } else {  // the plugin state the victim functions read (15_victims.cpp)
+            vector<uint8_t> raw;
+            if (!kbhip::debug_victim_table(s->s, n, raw)) throw kbhip::Error(KBHIP_EINVAL, "unknown table " + n);
+            if (out && cap_bytes >= (int64_t)raw.size() && !raw.empty()) std::memcpy(out, raw.data(), raw.size());
+            return (int64_t)raw.size();
         }
         const int64_t bytes = (int64_t)(v.size() * sizeof(int32_t));
         if (out && cap_bytes >= bytes && bytes) std::memcpy(out, v.data(), (size_t)bytes);

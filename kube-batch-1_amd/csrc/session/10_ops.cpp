@@ -171,7 +171,7 @@ int64_t apply_ops(Session& S, const uint8_t* op, const int32_t* pod, const int32
     struct VictGuard {  // a batch that fails part way leaves the victim-candidate table to be rebuilt
         Session& S;
         bool done = false;
-        ~VictGuard() { if (!done) S.vict_live = false; }
+        ~VictGuard() { if (!done) vict_stale(S); }
     } vict_guard{S};
     ov_quiesce(S);  // device work outside the batched pops' chain follows
     vector<NodeOp> ops;
@@ -179,6 +179,7 @@ int64_t apply_ops(Session& S, const uint8_t* op, const int32_t* pod, const int32
     apply_ops_model(S, op, pod, node, n, ops);
     int launches = launch_node_ops(S, ops);  // (a live victim-candidate table: its evictions in the same launch)
     if (S.vict_live) vict_apply_evictions(S, ops);
+    vs_mark_dirty(S, pod, n);  // (host lists only: the next kbhip_head_victims patches the victim state)
     vict_guard.done = true;
     launches += flush_tables(S);  // the evictions' / unevicts' predicate-target changes
     commit_marks(S, op, pod, n);

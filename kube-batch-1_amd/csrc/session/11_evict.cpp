@@ -239,17 +239,7 @@ struct EvictAction {
     // its job's queue and MinAvailable (read for every candidate of every visit)
     vector<vector<int>> vic_tiers;
     void compile_victims(bool preempt) {
-        for (auto& tier : S.tiers) {
-            vector<int> codes;
-            for (auto& pl : tier) {
-                if (pl.flags & (preempt ? KBS_DIS_PREEMPTABLE : KBS_DIS_RECLAIMABLE)) continue;
-                if (pl.name == "gang") codes.push_back(1);
-                else if (pl.name == "conformance") codes.push_back(2);
-                else if (preempt && pl.name == "drf" && S.drf_on) codes.push_back(3);
-                else if (!preempt && pl.name == "proportion" && S.prop_on) codes.push_back(4);
-            }
-            vic_tiers.push_back(std::move(codes));
-        }
+        vic_tiers = victim_tier_codes(S, preempt);
         const int P = (int)S.pods.size();
         if ((int)S.pod_queue.size() != P || S.pod_queue_gen != S.model_gen) {  // once per session model
             S.pod_queue.assign(P, -1);

@@ -17,10 +17,7 @@ size_t vict_tab_words(const Session& S) { return (S.queues.size() + 1) * 4 * (si
 // within the table's own size limit.
 void vict_build(Session& S) {
     const size_t Q = S.queues.size(), np = (size_t)S.nc.npad, words = vict_tab_words(S), bytes = words * sizeof(int64_t);
-    if (bytes > kVictMaxBytes)
-        throw Error(KBHIP_EUNSUPPORTED, "kbhip_rank_victim_nodes: the victim-candidate table of " + std::to_string(Q) +
-                                            " queues x " + std::to_string(np) + " nodes takes " +
-                                            std::to_string(bytes >> 20) + " MB, above the 512 MB limit");
+    vict_check_size(S);
     const int P = (int)S.pods.size(), N = S.n_total;
     int nth = P < (1 << 16) ? 1 : host_threads();
     nth = (int)std::max<size_t>(1, std::min<size_t>((size_t)nth, kVictMaxBytes / std::max<size_t>(bytes, 1)));
@@ -60,6 +57,14 @@ void vict_build(Session& S) {
 }
 
 }  // namespace
+
+void vict_check_size(const Session& S) {
+    const size_t Q = S.queues.size(), np = (size_t)S.nc.npad, bytes = vict_tab_words(S) * sizeof(int64_t);
+    if (bytes > kVictMaxBytes)
+        throw Error(KBHIP_EUNSUPPORTED, "kbhip_rank_victim_nodes: the victim-candidate table of " + std::to_string(Q) +
+                                            " queues x " + std::to_string(np) + " nodes takes " +
+                                            std::to_string(bytes >> 20) + " MB, above the 512 MB limit");
+}
 
 bool vict_ensure(Session& S) {
     if (S.vict_live) return false;
@@ -112,6 +117,44 @@ void vict_apply_evictions(Session& S, const vector<NodeOp>& ops) {
     }
 }
 
+// The job's own list of a call in a victim mode other than OTHER_QUEUES, uploaded (sums, then nodes, in
+// one copy: the previous call's copy ended with that call), and the call's VictArgs.
+VictArgs vict_args(Session& S, const HPod& p, int mode, vector<int32_t>& own_node, vector<int64_t>& own_sum) {
+    if (mode != KBHIP_VICTIMS_OTHER_QUEUES) vict_own_list(S, p.job, own_node, own_sum);
+    const size_t own_n = own_node.size(), own_bytes = own_n * (4 * sizeof(int64_t) + sizeof(int32_t));
+    if (own_n) {
+        S.h_vict_own.fit(own_bytes, std::max<size_t>(2 * own_bytes, 4096));
+        S.b_vict_own.grow(S.stream, own_bytes, std::max<size_t>(2 * own_bytes, 4096));
+        uint8_t* const h_own = S.h_vict_own.as<uint8_t>();
+        std::memcpy(h_own, own_sum.data(), own_n * 4 * sizeof(int64_t));
+        std::memcpy(h_own + own_n * 4 * sizeof(int64_t), own_node.data(), own_n * sizeof(int32_t));
+        HIPCHK(hipMemcpyAsync(S.b_vict_own.p, h_own, own_bytes, hipMemcpyHostToDevice, S.stream));
+    }
+    const uint8_t* d_own = (const uint8_t*)S.b_vict_own.p;
+    return VictArgs{(const int64_t*)S.b_vict.p,
+                    own_n ? (const int32_t*)(d_own + own_n * 4 * sizeof(int64_t)) : nullptr,
+                    own_n ? (const int64_t*)d_own : nullptr,
+                    S.nc.npad, (int32_t)S.queues.size(), S.jobs[p.job].queue, mode, (int32_t)own_n,
+                    p.ireq.c, p.ireq.m, p.ireq.g};
+}
+
+// The head of the walk of class cls, enqueued: afterwards (in stream order) b_rank_head holds the kTopK
+// best keys and the count.  Nothing is copied back or waited for.
+int rank_head_enqueue(Session& S, int cls, bool by_score, const VictArgs* v) {
+    const TaskClass& c = S.classes[cls];
+    int launches = 0;
+    if (!S.b_rank_head.p) S.b_rank_head.alloc<uint64_t>(rank_head_words());
+    ctrl_setup(S, 1, &cls, 0, 0, 0, 0, -1, 0);
+    launches += 1;
+    if (by_score && c.ipa_n > 0) {
+        HIPCHK(launch_ipa_minmax(S.nc, S.tab, S.d_ctrl, 0, S.stream));
+        launches += 1;
+    }
+    HIPCHK(launch_rank_head(S.conf, S.nc, S.tab, c, S.d_ctrl, by_score ? 1 : 0, v, (uint64_t*)S.b_rank_head.p,
+                            S.stream));
+    return launches + 2;  // sweep + merge
+}
+
 // Entries [first, first + cap) of the walk order of task `pod` (by_score:
 // preempt's SelectBestNode order, else reclaim's index order) and the number
 // of nodes in it.  mode 0 (kbhip_rank_nodes): every node of the order.  mode
@@ -137,44 +180,19 @@ int64_t rank_victim_nodes_abi(Session& S, int pod, bool by_score, int mode, int6
     const bool rebuilt = mode != 0 && vict_ensure(S);
     vector<int32_t> own_node;
     vector<int64_t> own_sum;
-    if (mode != 0 && mode != KBHIP_VICTIMS_OTHER_QUEUES) vict_own_list(S, p.job, own_node, own_sum);
-    const size_t own_n = own_node.size(), own_bytes = own_n * (4 * sizeof(int64_t) + sizeof(int32_t));
-    if (own_n) {  // sums, then nodes, in one copy (the previous call's copy ended with that call)
-        S.h_vict_own.fit(own_bytes, std::max<size_t>(2 * own_bytes, 4096));
-        S.b_vict_own.grow(S.stream, own_bytes, std::max<size_t>(2 * own_bytes, 4096));
-        uint8_t* const h_own = S.h_vict_own.as<uint8_t>();
-        std::memcpy(h_own, own_sum.data(), own_n * 4 * sizeof(int64_t));
-        std::memcpy(h_own + own_n * 4 * sizeof(int64_t), own_node.data(), own_n * sizeof(int32_t));
-        HIPCHK(hipMemcpyAsync(S.b_vict_own.p, h_own, own_bytes, hipMemcpyHostToDevice, S.stream));
-    }
     VictArgs v{};
     if (mode != 0) {
-        const uint8_t* d_own = (const uint8_t*)S.b_vict_own.p;
-        v = VictArgs{(const int64_t*)S.b_vict.p,
-                     own_n ? (const int32_t*)(d_own + own_n * 4 * sizeof(int64_t)) : nullptr,
-                     own_n ? (const int64_t*)d_own : nullptr,
-                     S.nc.npad, (int32_t)S.queues.size(), S.jobs[p.job].queue, mode, (int32_t)own_n,
-                     p.ireq.c, p.ireq.m, p.ireq.g};
+        v = vict_args(S, p, mode, own_node, own_sum);
         S.h_vict_out.fit(((size_t)N + 2) * sizeof(int32_t));
     }
     int32_t* const h_out = S.h_vict_out.as<int32_t>();  // victim modes: [0] the kept count, then the window's counts
-    const TaskClass& c = S.classes[cls];
     const uint64_t* keys = nullptr;  // entries [first, first + n_keys) of the order, on the host
     int64_t total = 0, n_keys = 0, launches = flush_tables(S);  // evictions / unevicts so far change pod-affinity predicates
     const bool head = cap > 0 && first <= kTopK && cap <= kTopK - first;
     if (head) {
-        if (!S.b_rank_head.p) S.b_rank_head.alloc<uint64_t>(rank_head_words());
         S.h_rank_head.fit((size_t)(kTopK + 1) * sizeof(uint64_t));
         uint64_t* const h_head = S.h_rank_head.as<uint64_t>();
-        ctrl_setup(S, 1, &cls, 0, 0, 0, 0, -1, 0);
-        launches += 1;
-        if (by_score && c.ipa_n > 0) {
-            HIPCHK(launch_ipa_minmax(S.nc, S.tab, S.d_ctrl, 0, S.stream));
-            launches += 1;
-        }
-        HIPCHK(launch_rank_head(S.conf, S.nc, S.tab, c, S.d_ctrl, by_score ? 1 : 0, mode ? &v : nullptr,
-                                (uint64_t*)S.b_rank_head.p, S.stream));
-        launches += 2;  // sweep + merge
+        launches += rank_head_enqueue(S, cls, by_score, mode ? &v : nullptr);
         HIPCHK(hipMemcpyAsync(h_head, S.b_rank_head.p, (size_t)(kTopK + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost,
                               S.stream));
         HIPCHK(hipStreamSynchronize(S.stream));

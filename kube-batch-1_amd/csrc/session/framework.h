@@ -546,6 +546,24 @@ struct Framework {
     }
 };
 
+// The victim functions of an action in tier order, as codes (1 gang, 2 conformance, 3 drf, 4 proportion;
+// the tiers' plugin names compared once, not per node visited): Preemptable's for preempt, else Reclaimable's.
+inline vector<vector<int>> victim_tier_codes(const Session& S, bool preempt) {
+    vector<vector<int>> out;
+    for (auto& tier : S.tiers) {
+        vector<int> codes;
+        for (auto& pl : tier) {
+            if (pl.flags & (preempt ? KBS_DIS_PREEMPTABLE : KBS_DIS_RECLAIMABLE)) continue;
+            if (pl.name == "gang") codes.push_back(1);
+            else if (pl.name == "conformance") codes.push_back(2);
+            else if (preempt && pl.name == "drf" && S.drf_on) codes.push_back(3);
+            else if (!preempt && pl.name == "proportion" && S.prop_on) codes.push_back(4);
+        }
+        out.push_back(std::move(codes));
+    }
+    return out;
+}
+
 // The order functions as heap comparators (util/priority_queue.go over Job / QueueOrderFn)
 struct JobLess {
     const Framework* F;

@@ -613,6 +613,23 @@ struct Session {
     bool vict_live = false;
     DevBuf b_vict, b_vict_own, b_vict_blk, b_vict_keys, b_vict_cands;
     PinnedBuf h_vict_own, h_vict_out;
+    // kbhip_head_victims (15_victims.cpp): the victim state (VictState, kbhip_internal.h) on the device.
+    // vs_live: it is current — built from the host model by the first call that needs it, cleared wherever
+    // vict_live is (vict_stale).  kbhip_apply_ops does not clear it: it appends the pods, jobs and queues it
+    // touched to vs_dirty_*, and the next kbhip_head_victims uploads those records and scatters them in one
+    // launch; more than vs_dirty_max pods waiting (option "victims_dirty_max") means a rebuild instead.
+    // vs_pos[pod] = the pod's place in the CSR (-1: none); vs_tasks / vs_max_tasks: its length and its
+    // longest node; vs_bytes: what the last build uploaded.  b_vs_spill: staging rows for nodes of more than
+    // kVictLds tasks; h_vs_patch / b_vs_patch: one call's patch lists; b_vs_out / h_vs_out: one call's head
+    // keys and rows.
+    bool vs_live = false;
+    vector<int32_t> vs_pos, vs_dirty_pod, vs_dirty_job, vs_dirty_queue;
+    int64_t vs_dirty_max = 1 << 16, vs_bytes = 0;
+    int32_t vs_tasks = 0, vs_max_tasks = 0;
+    double vs_build_s = 0;
+    DevBuf b_vs_off, b_vs_task, b_vs_job, b_vs_queue, b_vs_spill, b_vs_patch, b_vs_out;
+    PinnedBuf h_vs_patch, h_vs_out;
+    struct VictHost;  // the state on the host (15_victims.cpp)
     // kbhip_rank_heads (13_heads.cpp).  h_heads_in / b_heads_in: one call's upload — a PopCtrl image
     // of the call's own (slot i: request i's class, inter-pod min / max zero), its HeadDescs, the own-job
     // lists of its jobs; b_heads: the kernels' scratch (rank_heads_words); h_heads_out: kMaxChunk
@@ -845,10 +862,11 @@ struct Session {
         d_eng_tl = nullptr;
         eng_nw = 0;
         for (PinnedBuf* b : {&h_rank, &h_rank_head, &h_ops, &h_vict_own, &h_vict_out, &h_heads_in, &h_heads_out,
-                             &h_explain_in, &h_explain_out})
+                             &h_explain_in, &h_explain_out, &h_vs_patch, &h_vs_out})
             b->release();
         if (ev_ops) { (void)hipEventDestroy(ev_ops); ev_ops = nullptr; }
         vict_live = false;
+        vs_live = false;
         h_out = nullptr;
         if (cu_masked) {  // streams of option "cu_split" are this session's own
             for (int k = 1; k <= kMaxDep; ++k)
@@ -866,7 +884,8 @@ struct Session {
                           &b_arrive, &b_link, &b_dbg, &b_fit4, &b_rank_keys, &b_rank_sorted, &b_rank_tmp, &b_rank_cnt,
                           &b_rank_radix, &b_rank_head, &b_ops, &b_vict, &b_vict_own, &b_vict_blk, &b_vict_keys,
                           &b_vict_cands, &b_heads_in, &b_heads, &b_explain_in, &b_explain_part, &b_explain_out,
-                          &b_explain_v,
+                          &b_explain_v, &b_vs_off, &b_vs_task, &b_vs_job, &b_vs_queue, &b_vs_spill, &b_vs_patch,
+                          &b_vs_out,
                           &b_shard_send, &b_shard_recv, &b_tab_idx, &b_sweep_cnt, &b_dd_max, &b_cmp_mask, &b_cmp_blk,
                           &b_cmp_node, &b_cmp_val})
             b->release();
@@ -1213,7 +1232,14 @@ const HPod& query_task(const Session& S, int pod, const string& prefix, bool nee
 void query_begin(Session& S, const char* api_name);
 // kbhip_rank_victim_nodes (12_rank.cpp).  vict_stale: the call that follows changes pod statuses outside
 // kbhip_apply_ops — the victim-candidate table is rebuilt by the next ranking that needs it.
-inline void vict_stale(Session& S) { S.vict_live = false; }
+// The victim state of kbhip_head_victims (15_victims.cpp) goes stale with it, and its dirty lists end.
+inline void vict_stale(Session& S) {
+    S.vict_live = false;
+    S.vs_live = false;
+    S.vs_dirty_pod.clear();
+    S.vs_dirty_job.clear();
+    S.vs_dirty_queue.clear();
+}
 // A candidate victim: Running with a Running copy on its node, and a job (EvictAction::build_node_tasks' run_copy).
 inline bool vict_candidate(const Session& S, const HPod& p) {
     return p.status == Running && !p.node_rel && p.job >= 0 && on_node_of(p) && p.node < S.n_total;
@@ -1227,6 +1253,7 @@ int64_t rank_victim_nodes_abi(Session& S, int pod, bool by_score, int mode, int6
 // live (true: built now).  vict_own_list: job jb's candidates per node, distinct nodes ascending with four
 // sums each.  vict_count_host: vict_cand's count of node n on the host copy of the table.
 bool vict_ensure(Session& S);
+void vict_check_size(const Session& S);  // refuses a candidate table above its limit (KBHIP_EUNSUPPORTED)
 void vict_own_list(const Session& S, int jb, vector<int32_t>& node, vector<int64_t>& sum);
 int64_t vict_count_host(const Session& S, int mode, int q, const vector<int32_t>& own_node,
                         const vector<int64_t>& own_sum, int n);
@@ -1238,6 +1265,21 @@ int64_t apply_ops(Session& S, const uint8_t* op, const int32_t* pod, const int32
 int64_t explain_tasks_abi(Session& S, const int32_t* task_ids, int n_tasks, uint8_t* out_verdict, int64_t* out_hist,
                           int64_t* out_info);
 void debug_explain(const Session& S, int pod, uint8_t* out_verdict, int64_t* out_hist);
+// kbhip_head_victims (15_victims.cpp).  vs_mark_dirty: a batch of kbhip_apply_ops that reached the host
+// model (a live state only).  debug_victim_table: kbhip_debug_table's plugin-state tables; false: not one.
+int64_t head_victims_abi(Session& S, int pod, bool by_score, int mode, int cap, int stride, int32_t* out_node,
+                         int32_t* out_score, int32_t* out_count, int32_t* out_evict, uint8_t* out_flags,
+                         int32_t* out_victim, int64_t* out_info);
+void vs_mark_dirty(Session& S, const int32_t* pod, int64_t n);
+void debug_victims(Session& S, int pod, int mode, int node, int stride, int32_t* out_count, int32_t* out_evict,
+                   uint8_t* out_flags, int32_t* out_victim);
+bool debug_victim_table(Session& S, const string& name, vector<uint8_t>& out);
+// The head path of rank_victim_nodes_abi, shared with kbhip_head_victims.  vict_args: the job's own list
+// uploaded and the call's VictArgs.  rank_head_enqueue: the control block, the inter-pod prepass where the
+// class has one, the sweep and the merge on the session's stream (b_rank_head holds the result once they
+// ran); returns the launches it made.
+VictArgs vict_args(Session& S, const HPod& p, int mode, vector<int32_t>& own_node, vector<int64_t>& own_sum);
+int rank_head_enqueue(Session& S, int cls, bool by_score, const VictArgs* v);
 
 }  // namespace kbhip
 

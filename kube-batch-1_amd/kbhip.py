@@ -23,6 +23,7 @@ STOP_ALL, STOP_UNASSIGNED, STOP_READY = 0, 1, 2
 OP_EVICT, OP_PIPELINE, OP_UNPIPELINE, OP_UNEVICT = 1, 2, 3, 4  # kbhip_apply_ops
 VICTIMS_OTHER_QUEUES, VICTIMS_QUEUE_OTHER_JOBS, VICTIMS_SAME_JOB = 1, 2, 3  # kbhip_rank_victim_nodes
 RANK_HEADS_MAX = 64  # KBHIP_RANK_HEADS_MAX: tasks per kbhip_rank_heads
+HEAD_VICTIMS_VALID, HEAD_VICTIMS_COVERS = 1, 2  # kbhip_head_victims: out_flags bits
 # kbhip_explain_tasks: the verdict codes (low four bits of a verdict byte), the short bits of codes 0..2
 (WHY_FITS_IDLE, WHY_FITS_RELEASING, WHY_RESOURCES, WHY_POD_COUNT, WHY_NODE_SELECTOR, WHY_HOST_PORTS,
  WHY_UNSCHEDULABLE, WHY_TAINTS, WHY_POD_AFFINITY, WHY_SCORE_ERROR) = range(10)
@@ -41,7 +42,7 @@ EXPORTS = ("kbhip_device_count", "kbhip_session_open", "kbhip_session_open_file"
            "kbhip_place_job_wait", "kbhip_place_job_cancel", "kbhip_time_sweeps", "kbhip_time_rank_multi",
            "kbhip_session_carry_snapshot", "kbhip_walk_visits", "kbhip_fit_deltas", "kbhip_rank_nodes",
            "kbhip_apply_ops", "kbhip_rank_victim_nodes", "kbhip_rank_heads", "kbhip_explain_tasks",
-           "kbhip_debug_explain")
+           "kbhip_debug_explain", "kbhip_head_victims", "kbhip_debug_victims")
 
 RED_MAX_U64, RED_MIN_I64, RED_MAX_I64, RED_SUM_I64 = 0, 1, 2, 3
 ALLREDUCE_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint64), ctypes.c_int32,
@@ -150,6 +151,9 @@ def lib() -> ctypes.CDLL:
         L.kbhip_explain_tasks.argtypes = [vp, vp, i32, vp, vp, vp]
         L.kbhip_explain_tasks.restype = i64
         L.kbhip_debug_explain.argtypes = [vp, i32, vp, vp]
+        L.kbhip_head_victims.argtypes = [vp, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp]
+        L.kbhip_head_victims.restype = i64
+        L.kbhip_debug_victims.argtypes = [vp, i32, i32, i32, i32, vp, vp, vp, vp]
         _lib = L
     return _lib
 
@@ -317,6 +321,31 @@ class Session:
         shape = (n, max(cap, 0))
         return (total[:n].copy(), node[: n * cap].reshape(shape), score[: n * cap].reshape(shape),
                 cands[: n * cap].reshape(shape), info)
+
+    def head_victims(self, task_id: int, by_score: bool = True, victims: int = VICTIMS_OTHER_QUEUES,
+                     cap: int = 64, stride: int = 16):
+        """kbhip_head_victims: the head of rank_victim_nodes' walk and, per head
+        node, what Reclaimable / Preemptable, validateVictims and the eviction
+        loop decide on it: (total, nodes[cap], scores[cap], counts[cap],
+        evicts[cap], flags[cap], victim_rows[cap, stride], info).  Rows beyond
+        min(cap, total) are -1 / 0.  A victim row holds the first min(count,
+        stride) victims' pod indices, then -1.
+        info: {"rebuilt", "state_rebuilt", "patched", "launches", "max_count"}."""
+        cap, stride = int(cap), int(stride)
+        rows = max(cap, 1)
+        node = np.full(rows, -1, np.int32)
+        score = np.zeros(rows, np.int32)
+        count = np.zeros(rows, np.int32)
+        evict = np.zeros(rows, np.int32)
+        flags = np.zeros(rows, np.uint8)
+        victim = np.full(rows * max(stride, 1), -1, np.int32)
+        info = np.zeros(5, np.int64)
+        n = int(lib().kbhip_head_victims(self._h, int(task_id), int(by_score), int(victims), cap, stride, _p(node),
+                                         _p(score), _p(count), _p(evict), _p(flags), _p(victim), _p(info)))
+        _check(n if n < 0 else 0)
+        return (n, node[:cap], score[:cap], count[:cap], evict[:cap], flags[:cap],
+                victim[: cap * stride].reshape(cap, stride),
+                dict(zip(("rebuilt", "state_rebuilt", "patched", "launches", "max_count"), map(int, info))))
 
     def explain_tasks(self, task_ids, verdicts: bool = False, n_nodes: Optional[int] = None):
         """kbhip_explain_tasks: why each node is, or is not, in the allocate
@@ -533,6 +562,16 @@ class Session:
         _check(int(lib().kbhip_debug_table(self._h, name.encode(), _p(out), out.nbytes)) if n > 0 else 0)
         return out[: int(n) // 4]
 
+    def table_raw(self, name: str, dtype) -> np.ndarray:
+        """A table of another element type (job_drf_alloc, queue_allocated, queue_deserved: float64;
+        victim_state: int64)."""
+        n = int(lib().kbhip_debug_table(self._h, name.encode(), None, 0))
+        _check(n if n < 0 else 0)
+        out = np.zeros(max(n // np.dtype(dtype).itemsize, 1), dtype)
+        if n:
+            _check(int(lib().kbhip_debug_table(self._h, name.encode(), _p(out), out.nbytes)))
+        return out[: n // np.dtype(dtype).itemsize]
+
     def gang_unschedulable(self) -> dict:
         """The gang plugin's OnSessionClose messages: {job uid: message} for
         every job not Ready (kbhip_gang_unschedulable)."""
@@ -590,6 +629,16 @@ class EncodedSnapshot:
         hist = np.zeros(EXPLAIN_BINS, np.int64)
         _check(lib().kbhip_debug_explain(self._h, int(task_id), _p(verdict), _p(hist)))
         return verdict[:n_nodes].copy(), hist
+
+    def victims(self, task_id: int, victims: int, node: int, stride: int = 256):
+        """kbhip_debug_victims: (count, evict, flags, victims[min(count, stride)])
+        of one node, by the kernel's own per-node functions on the host tables."""
+        count, evict = np.zeros(1, np.int32), np.zeros(1, np.int32)
+        flags = np.zeros(1, np.uint8)
+        row = np.full(max(int(stride), 1), -1, np.int32)
+        _check(lib().kbhip_debug_victims(self._h, int(task_id), int(victims), int(node), int(stride), _p(count),
+                                         _p(evict), _p(flags), _p(row)))
+        return int(count[0]), int(evict[0]), int(flags[0]), row[: min(int(count[0]), int(stride))].copy()
 
     def replay(self, pods, modes, nodes, kinds) -> np.ndarray:
         """Per-step, per-node selection keys along a given decision sequence
