@@ -428,6 +428,53 @@ func (e *Engine) HeadVictims(task int32, byScore bool, victims int32, cap, strid
 	return int64(t), heads, info, nil
 }
 
+// The stop reasons of WalkVictims (KBHIP_WALK_*).
+const (
+	WalkAssigned  = int(C.KBHIP_WALK_ASSIGNED)  // a node covered InitResreq: the last op pipelines the task
+	WalkExhausted = int(C.KBHIP_WALK_EXHAUSTED) // every node of the walk was visited, none covered
+	WalkHeadEnd   = int(C.KBHIP_WALK_HEAD_END)  // cap entries or the 64-entry head used up, the walk has more nodes
+	WalkCapacity  = int(C.KBHIP_WALK_CAPACITY)  // the next step does not fit capOps or the carried state
+)
+
+// WalkVictimsInfo says how a WalkVictims call ended and what it did (out_info
+// of kbhip_walk_victims).
+type WalkVictimsInfo struct {
+	Stop         int   // a Walk* reason
+	Total        int64 // nodes in the pruned walk
+	Visited      int64 // head entries decided
+	Acted        int64 // nodes evicted from
+	LastNode     int32 // the last acted-on node, -1 if none: where a resumed call goes on
+	LastScore    int32 // its score (0 with byScore false)
+	Launches     int64
+	Rebuilt      bool  // the candidate table was built by this call
+	StateRebuilt bool  // the victim state was built by this call
+	Patched      int64 // records of earlier ApplyOps batches patched into it
+}
+
+// WalkVictims runs one task's whole eviction walk over the head of its pruned
+// walk (kbhip_walk_victims): the node loop of preempt() / reclaim with the
+// evictions of each node carried to the next.  ops / pods / nodes go to
+// ApplyOps unchanged.  afterNode < 0 starts at the top; after a WalkCapacity
+// or WalkHeadEnd stop apply the ops and call again with LastNode / LastScore.
+// 1 <= cap <= 64, capOps >= 1.
+func (e *Engine) WalkVictims(task int32, byScore bool, victims int32, cap int, afterNode, afterScore int32, capOps int) (ops []uint8, pods, nodes []int32, info WalkVictimsInfo, err error) {
+	if cap < 1 || cap > 64 || capOps < 1 { // (also keeps &x[0] below off empty slices)
+		return nil, nil, nil, info, fmt.Errorf("kbhip walk_victims: cap %d (1..64), capOps %d (>= 1)", cap, capOps)
+	}
+	ops, pods, nodes = make([]uint8, capOps), make([]int32, capOps), make([]int32, capOps)
+	var raw [8]C.int64_t
+	n := C.kbhip_walk_victims(e.s, C.int32_t(task), boolI32(byScore), C.int32_t(victims), C.int32_t(cap),
+		C.int32_t(afterNode), C.int32_t(afterScore), (*C.uint8_t)(unsafe.Pointer(&ops[0])),
+		(*C.int32_t)(unsafe.Pointer(&pods[0])), (*C.int32_t)(unsafe.Pointer(&nodes[0])), C.int64_t(capOps), &raw[0])
+	if n < 0 {
+		return nil, nil, nil, info, lastErr("walk_victims", C.int(n))
+	}
+	info = WalkVictimsInfo{Stop: int(raw[0]), Total: int64(raw[1]), Visited: int64(raw[2]), Acted: int64(raw[3]),
+		LastNode: int32(raw[4]), LastScore: int32(raw[5]), Launches: int64(raw[6]), Rebuilt: raw[7]&1 != 0,
+		StateRebuilt: raw[7]&2 != 0, Patched: int64(raw[7]) >> 8}
+	return ops[:n], pods[:n], nodes[:n], info, nil
+}
+
 // The verdict codes of ExplainTasks (KBHIP_WHY_*): the low four bits of a
 // verdict byte; the WhyShort* bits accompany the codes 0..2.
 const (

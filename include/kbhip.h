@@ -444,6 +444,70 @@ int64_t kbhip_head_victims(kb_session* s, int32_t task_id, int32_t by_score, int
                            int32_t* out_evict, uint8_t* out_flags, int32_t* out_victim /* cap rows of stride */,
                            int64_t* out_info /* optional */);
 
+/* kbhip_walk_victims <- one task's whole node loop of preempt()
+ * (preempt.go:259-353) or of reclaim (reclaim.go:115-189) over the head of its
+ * pruned walk, in one call: the finished batch for kbhip_apply_ops.
+ * The head is the one kbhip_head_victims(task, by_score, victims, ..) ranks for
+ * the session as it stands.  Its entries are visited in order, and on each the
+ * call decides what kbhip_head_victims' row says — against the plugin state as
+ * the evictions of the earlier entries of this same call leave it:
+ *   no KBHIP_HEAD_VICTIMS_VALID  the node is passed over.
+ *   KBHIP_HEAD_VICTIMS_VALID     one KBHIP_OP_EVICT per victim of the evicted
+ *     prefix is appended, in victim order, out_node = that node.
+ *   and KBHIP_HEAD_VICTIMS_COVERS  KBHIP_OP_PIPELINE task, node follows and the
+ *     walk stops with KBHIP_WALK_ASSIGNED.
+ *   otherwise  the evictions are carried — each victim's job: drf's allocation
+ *     minus Resreq, gang's readyTaskNum minus one; its queue: proportion's
+ *     allocation minus Resreq; with KBHIP_VICTIMS_SAME_JOB the preemptor's own
+ *     allocation too (drf.go:88-90) — and the walk goes on: the reference's
+ *     loop evicts from such a node and tries the next one.
+ * Returns the ops written.  out_op / out_pod / out_node can be passed unchanged
+ * to kbhip_apply_ops; that batch leaves the session where the reference's loop
+ * leaves it for this task.  The walk order is fixed before the first eviction
+ * (no ranking reads Releasing), as the reference ranks once per task.
+ * `cap` bounds the head entries decided in this call.  after_node >= 0 resumes:
+ * head entries whose key is not below the key the head sweep forms for
+ * (after_score, after_node) — the score is ignored with by_score 0, where the
+ * sweep's keys carry none — are passed over undecided and uncounted: the nodes
+ * the loop has left behind.  A host resumes after KBHIP_WALK_CAPACITY (apply the
+ * ops, call again after out_info[4] / out_info[5]) and after
+ * KBHIP_WALK_HEAD_END while the resume point is inside the new 64-entry head;
+ * past the head it falls back to kbhip_rank_victim_nodes windows and its own
+ * victim functions.
+ * A step is all or nothing: when a valid node's prefix plus one slot for a
+ * possible pipeline does not fit what is left of cap_ops, or a node the walk
+ * would go on from touches more distinct jobs or queues than the carried state
+ * holds (256 jobs, 64 queues; option "walk_overlay_max" = k, tests, lowers
+ * both to k, 0 = full), the walk stops before that node with
+ * KBHIP_WALK_CAPACITY and the ops written are a prefix of the uncapped answer.
+ * So that a resumed walk always moves on, the first node a call acts on is
+ * taken even when the carried state cannot hold what it touches: its ops are
+ * written and the walk stops behind it with KBHIP_WALK_CAPACITY.  (cap_ops
+ * below the first step's need has no such way out: KBHIP_WALK_CAPACITY with
+ * no node acted on asks for a larger cap_ops.)
+ * out_info (optional, 8 entries): [0] the stop reason, [1] the total of the
+ * pruned walk (kbhip_head_victims' return value), [2] head entries decided,
+ * [3] nodes acted on, [4] the last acted-on node (-1: none), [5] its score (0
+ * with by_score 0 or none), [6] kernel launches (kbhip_head_victims' head
+ * launches, then one), [7] bit 0: the candidate table was rebuilt, bit 1: the
+ * victim state was rebuilt, bits 8 and up: the records patched into it.
+ * Read-only as kbhip_head_victims: the carried state lives inside the launch
+ * and is discarded; the call changes the currency of the two tables and the
+ * plugins' open state, nothing else.  The whole call is validated before any
+ * device work, and a refused call writes nothing.  KBHIP_EINVAL: as
+ * kbhip_head_victims, cap_ops < 1, a null out_op, out_pod or out_node,
+ * after_node outside -1 .. nodes - 1.  KBHIP_EUNSUPPORTED: where
+ * kbhip_head_victims refuses. */
+#define KBHIP_WALK_ASSIGNED  1 /* a node covered InitResreq: the last op is the task's KBHIP_OP_PIPELINE */
+#define KBHIP_WALK_EXHAUSTED 2 /* every node of the walk was visited, none covered */
+#define KBHIP_WALK_HEAD_END  3 /* `cap` head entries (or the 64-entry head) used up, the walk has more nodes */
+#define KBHIP_WALK_CAPACITY  4 /* the next node's evictions would not fit cap_ops, or the carried state is full */
+int64_t kbhip_walk_victims(kb_session* s, int32_t task_id, int32_t by_score, int32_t victims /* KBHIP_VICTIMS_* */,
+                           int32_t cap /* 1..64 head entries to visit */,
+                           int32_t after_node /* -1: from the top */, int32_t after_score,
+                           uint8_t* out_op, int32_t* out_pod, int32_t* out_node, int64_t cap_ops,
+                           int64_t* out_info /* optional, 8 */);
+
 /* kbhip_explain_tasks <- why each node is, or is not, a node of the allocate
  * walk of up to KBHIP_EXPLAIN_MAX pending tasks, on the session as it stands:
  * what the reference logs node by node (allocate.go:128-137, the error
@@ -838,6 +902,19 @@ int kbhip_debug_explain(kb_session* s, int32_t task_id, uint8_t* out_verdict, in
  * 1..3, a node out of range, stride < 1. */
 int kbhip_debug_victims(kb_session* s, int32_t task_id, int32_t victims, int32_t node, int32_t stride,
                         int32_t* out_count, int32_t* out_evict, uint8_t* out_flags, int32_t* out_victim);
+/* Test support: kbhip_walk_victims' node loop over the caller's node list
+ * (n_nodes entries, visited in the given order, whether or not they are in the
+ * task's walk) on an encode-only session's host tables, by the functions the
+ * kernel runs (vict_stage_walk, vict_link, walk_step, kbhip_eval.h).  Returns
+ * the ops written; out_op / out_pod / out_node as that call defines them;
+ * out_info (optional, 8): the stop reason (never KBHIP_WALK_HEAD_END), n_nodes,
+ * the entries visited, the nodes acted on, the last acted-on node, then zeros.
+ * Option "walk_overlay_max" applies.  KBHIP_EINVAL: a null session, output or
+ * node list, a session with a device, a task without a class or a job,
+ * victims outside 1..3, a node out of range, n_nodes < 0, cap_ops < 1. */
+int64_t kbhip_debug_walk_victims(kb_session* s, int32_t task_id, int32_t victims, const int32_t* nodes,
+                                 int32_t n_nodes, int64_t cap_ops, uint8_t* out_op, int32_t* out_pod,
+                                 int32_t* out_node, int64_t* out_info);
 
 const char* kbhip_last_error(void);
 

@@ -652,5 +652,121 @@ KBHIP_HD int vict_decide(const VictHdr& h, VictRec* rec, int n, int stride, int3
     return alive;
 }
 
+// ---------------------------------------------------------------------------
+// One task's eviction walk (kbhip_walk_victims, kbhip_debug_walk_victims): the
+// node loop of preempt.go:259-353 / reclaim.go:115-189 over a list of nodes.
+// A node whose victims are valid but do not cover InitResreq is evicted from
+// and the loop goes on; the next node's victim functions see those evictions
+// through the overlay (kbhip_internal.h) — what on_deallocate / set_status
+// (framework.h) do to the job's and the queue's records:
+//   walk_ov_job / walk_ov_queue   the entry of an id, or -1
+//   vict_stage_walk  vict_stage, then the overlay's deltas on the candidate's
+//                    job and queue records
+//   walk_step        sequential: vict_decide on the staged node, the capacity
+//                    test (a step is all or nothing), the ops, and the evicted
+//                    prefix folded into the overlay and, for the task's own
+//                    job, into VictHdr::la
+// ---------------------------------------------------------------------------
+KBHIP_HD void walk_ov_init(WalkOverlay& ov, int cap_j, int cap_q) {
+    ov.n_j = ov.n_q = 0;
+    ov.cap_j = cap_j < 1 ? 1 : (cap_j > kWalkOvJobs ? kWalkOvJobs : cap_j);
+    ov.cap_q = cap_q < 1 ? 1 : (cap_q > kWalkOvQueues ? kWalkOvQueues : cap_q);
+}
+KBHIP_HD int walk_ov_job(const WalkOverlay& ov, int id) {
+    for (int i = 0; i < ov.n_j; ++i) if (ov.j_id[i] == id) return i;
+    return -1;
+}
+KBHIP_HD int walk_ov_queue(const WalkOverlay& ov, int id) {
+    for (int i = 0; i < ov.n_q; ++i) if (ov.q_id[i] == id) return i;
+    return -1;
+}
+// the entry of an id, added (with nothing taken off yet) where it is new; -1: the table is full
+KBHIP_HD int walk_ov_job_slot(WalkOverlay& ov, int id) {
+    int i = walk_ov_job(ov, id);
+    if (i >= 0 || ov.n_j >= ov.cap_j) return i;
+    i = ov.n_j++;
+    ov.j_id[i] = id;
+    ov.j_gone[i] = 0;
+    for (int x = 0; x < 3; ++x) ov.j_sub[i][x] = 0;
+    return i;
+}
+KBHIP_HD int walk_ov_queue_slot(WalkOverlay& ov, int id) {
+    int i = walk_ov_queue(ov, id);
+    if (i >= 0 || ov.n_q >= ov.cap_q) return i;
+    i = ov.n_q++;
+    ov.q_id[i] = id;
+    for (int x = 0; x < 3; ++x) ov.q_sub[i][x] = 0;
+    return i;
+}
+KBHIP_HD void vict_stage_walk(const VictState& st, const VictHdr& h, const WalkOverlay& ov, int at, VictRec& r) {
+    vict_stage(st, h, at, r);
+    if (!r.cand) return;
+    const int ji = walk_ov_job(ov, r.t.job);
+    if (ji >= 0) {
+        r.ready -= ov.j_gone[ji];
+        for (int x = 0; x < 3; ++x) r.jalloc[x] -= (double)ov.j_sub[ji][x];
+    }
+    const int qi = r.t.queue >= 0 ? walk_ov_queue(ov, r.t.queue) : -1;
+    if (qi >= 0)
+        for (int x = 0; x < 3; ++x) r.qalloc[x] -= (double)ov.q_sub[qi][x];
+}
+// rec[0 .. n): node `node` (its walk score `score`) staged by vict_stage_walk and linked.  Appends the
+// node's ops at out_pod / out_node [c.n_ops ..) and moves c on; c.stop != 0 ends the walk.
+KBHIP_HD void walk_step(VictHdr& h, WalkOverlay& ov, WalkCtl& c, VictRec* rec, int n, int node, int score,
+                        int32_t* out_pod, int32_t* out_node) {
+    int32_t evict = 0, flags = 0;
+    c.visited += 1;
+    (void)vict_decide(h, rec, n, 0, nullptr, &evict, &flags);
+    if (!(flags & 1)) return;  // validateVictims fails: the loop goes on to the next node
+    if (c.n_ops + evict + 1 > c.cap_ops) { c.stop = kWalkCapacity; return; }
+    const bool covers = (flags & 2) != 0;
+    bool carry = !covers;
+    if (carry) {  // the walk goes on: the prefix's jobs and queues need their entries (none is kept if one is missing)
+        const int nj = ov.n_j, nq = ov.n_q;
+        bool full = false;
+        for (int k = 0, e = 0; k < n && e < evict && !full; ++k) {
+            if (!rec[k].alive) continue;
+            ++e;
+            full = walk_ov_job_slot(ov, rec[k].t.job) < 0 ||
+                   (rec[k].t.queue >= 0 && walk_ov_queue_slot(ov, rec[k].t.queue) < 0);
+        }
+        if (full) {
+            ov.n_j = nj;
+            ov.n_q = nq;
+            if (c.acted > 0) { c.stop = kWalkCapacity; return; }
+            carry = false;  // the first step of a call is taken whatever it touches, and the walk stops behind it
+        }
+    }
+    for (int k = 0, e = 0; k < n && e < evict; ++k) {
+        const VictRec& r = rec[k];
+        if (!r.alive) continue;
+        ++e;
+        out_pod[c.n_ops] = r.t.pod;
+        out_node[c.n_ops] = node;
+        c.n_ops += 1;
+        if (!carry) continue;
+        const int ji = walk_ov_job(ov, r.t.job);
+        ov.j_gone[ji] += 1;
+        for (int x = 0; x < 3; ++x) ov.j_sub[ji][x] += r.t.req[x];
+        if (r.t.queue >= 0) {
+            const int qi = walk_ov_queue(ov, r.t.queue);
+            for (int x = 0; x < 3; ++x) ov.q_sub[qi][x] += r.t.req[x];
+        }
+        if (r.t.job == h.job)  // (KBHIP_VICTIMS_SAME_JOB only) drf.go:88-90: the preemptor's job allocation
+            for (int x = 0; x < 3; ++x) h.la[x] -= (double)r.t.req[x];
+    }
+    c.acted += 1;
+    c.last_node = node;
+    c.last_score = score;
+    if (covers) {
+        out_pod[c.n_ops] = c.task;
+        out_node[c.n_ops] = node;
+        c.n_ops += 1;
+        c.stop = kWalkAssigned;
+    } else if (!carry) {
+        c.stop = kWalkCapacity;
+    }
+}
+
 
 }  // namespace kbhip

@@ -279,6 +279,39 @@ struct VictPatch {
 };
 hipError_t launch_victims_patch(const VictState& st, const VictPatch& p, hipStream_t stm);
 
+// kbhip_walk_victims (k_walk_victims, kbhip_victims.hip): one task's eviction walk over the head.  The
+// evictions of a node that is valid but does not cover InitResreq change what the victim functions read on
+// the nodes after it; the walk carries those changes in an overlay over the victim state instead of
+// writing them: per touched job the evicted Resreq sum (off drf's allocation) and the evicted count (off
+// gang's readyTaskNum), per touched queue the evicted Resreq sum (off proportion's allocation).  Short
+// lists keyed by id, searched linearly; Resreq sums are integers, so the sums are exact and the order of
+// the subtractions does not matter.  cap_j / cap_q: the capacities in force (option "walk_overlay_max").
+constexpr int kWalkOvJobs = 256, kWalkOvQueues = 64;
+struct WalkOverlay {
+    int32_t n_j, n_q, cap_j, cap_q;
+    int32_t j_id[kWalkOvJobs], j_gone[kWalkOvJobs];
+    int64_t j_sub[kWalkOvJobs][3];
+    int32_t q_id[kWalkOvQueues];
+    int64_t q_sub[kWalkOvQueues][3];
+};
+// The walk's progress and result words (kbhip.h: out_info[0 .. 5], the op count).  stop: 0 while the walk
+// goes on, else the KBHIP_WALK_* reason.
+constexpr int32_t kWalkAssigned = 1, kWalkExhausted = 2, kWalkHeadEnd = 3, kWalkCapacity = 4;
+struct WalkCtl {
+    int64_t n_ops, cap_ops;
+    int32_t stop, visited, acted, last_node, last_score, task;
+};
+// One block.  head: launch_rank_head's result (keys, then the count).  Visits up to `cap` head entries
+// whose key is below after_key (0: from the top), stages each node against st under the overlay and runs
+// walk_step (kbhip_eval.h).  out_info (8 int64): stop, total, visited, acted, last node, last score, ops,
+// 0; out_pod / out_node: cap_ops entries each — every op is an eviction of out_pod on out_node but the last
+// one of a walk that stopped KBHIP_WALK_ASSIGNED, which pipelines `task` there.  spill: one row of
+// spill_stride records for nodes of more than kVictLds tasks.
+hipError_t launch_walk_victims(const VictState& st, const VictHdr& h, const uint64_t* head, int cap, uint64_t after_key,
+                               int task, int node_base, VictRec* spill, int spill_stride, int ov_cap_j, int ov_cap_q,
+                               int64_t cap_ops, int64_t* out_info, int32_t* out_pod, int32_t* out_node,
+                               hipStream_t stm);
+
 // Selection-key format of a batched launch: 32-bit keys when the class's
 // score range and the node count fit (kbhip_kernels.hip, PopArgs).
 struct KeyFormat {

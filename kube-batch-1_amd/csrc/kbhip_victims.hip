@@ -22,6 +22,10 @@
 //                    function.  The lanes fill the victim row's tail with -1.
 //                    Block 0 also copies the head's keys and count, so that
 //                    one copy back returns everything.
+//   k_walk_victims   kbhip_walk_victims: one block walks the head entries in
+//                    order, staging each node as above under an overlay of
+//                    the evictions of the entries before it (described at the
+//                    kernel).
 //   k_victims_patch  the records kbhip_apply_ops left dirty, one thread each.
 // Stores are plain vector stores; nothing is atomic, no block waits for another.
 #include <hip/hip_runtime.h>
@@ -90,6 +94,76 @@ __global__ __launch_bounds__(256) void k_victims_patch(VictTask* task, VictJob* 
         const int q = p.q_id[i];
         if (q >= 0 && q < n_queues) queue[q] = p.q_rec[i];
     }
+}
+
+// kbhip_walk_victims: the node loop of one task over the head, one block of kWalkBlock threads.  The loop
+// over the head entries is sequential by its definition (entry i + 1 reads what entry i evicted); inside
+// an entry the threads stage and link the node's records under the overlay, thread 0 runs walk_step (the
+// decision, the ops, the fold: the evicted prefix is a few tasks, and the fold keeps the job's entries in
+// victim order), and a barrier hands the overlay to the next entry.  Records, overlay, header and progress
+// live in LDS (43 KB + 9 KB); nothing is prefetched for the next entry while thread 0 decides.
+constexpr int kWalkBlock = 256;
+__global__ __launch_bounds__(kWalkBlock) void k_walk_victims(VictState st, VictHdr h0, const uint64_t* head, int cap,
+                                                             uint64_t after_key, int task, int node_base,
+                                                             VictRec* spill, int spill_stride, int ov_cap_j,
+                                                             int ov_cap_q, int64_t cap_ops, int64_t* out_info,
+                                                             int32_t* out_pod, int32_t* out_node) {
+    __shared__ VictRec s_rec[kVictLds];
+    __shared__ WalkOverlay s_ov;
+    __shared__ VictHdr s_h;
+    __shared__ WalkCtl s_c;
+    const int tid = threadIdx.x;
+    if (tid == 0) {
+        s_h = h0;
+        walk_ov_init(s_ov, ov_cap_j, ov_cap_q);
+        s_c = WalkCtl{0, cap_ops, 0, 0, 0, -1, 0, task};
+    }
+    __syncthreads();
+    const uint64_t total = head[kTopK];
+    const int in_head = total < (uint64_t)kTopK ? (int)total : kTopK;
+    int i = 0;
+    for (; i < in_head; ++i) {  // (every condition below is uniform over the block)
+        if (s_c.visited >= cap) break;
+        const uint64_t key = head[i];
+        if (after_key != 0 && key >= after_key) continue;  // the loop has left this node behind
+        const int node = key_idx(key) - node_base;
+        int off = 0, n = 0;  // n == 0: nothing to stage (walk_step still counts the visit)
+        if (key != 0 && node >= 0 && node < st.n_nodes) {
+            off = st.node_off[node];
+            n = st.node_off[node + 1] - off;
+            if (off < 0 || n < 0 || off + n > st.n_tasks || (n > kVictLds && (!spill || n > spill_stride))) n = 0;
+        }
+        VictRec* const rec = n <= kVictLds ? s_rec : spill;
+        for (int k = tid; k < n; k += kWalkBlock) vict_stage_walk(st, s_h, s_ov, off + k, rec[k]);
+        __syncthreads();
+        for (int k = tid; k < n; k += kWalkBlock) vict_link(rec, k);
+        __syncthreads();
+        if (tid == 0) walk_step(s_h, s_ov, s_c, rec, n, key_idx(key), key_score(key), out_pod, out_node);
+        __syncthreads();
+        if (s_c.stop != 0) break;
+    }
+    if (tid == 0) {
+        int stop = s_c.stop;
+        if (stop == 0) stop = (uint64_t)i < total ? kWalkHeadEnd : kWalkExhausted;
+        out_info[0] = stop;
+        out_info[1] = (int64_t)total;
+        out_info[2] = s_c.visited;
+        out_info[3] = s_c.acted;
+        out_info[4] = s_c.last_node;
+        out_info[5] = s_c.last_score;
+        out_info[6] = s_c.n_ops;
+        out_info[7] = 0;
+    }
+}
+
+hipError_t launch_walk_victims(const VictState& st, const VictHdr& h, const uint64_t* head, int cap, uint64_t after_key,
+                               int task, int node_base, VictRec* spill, int spill_stride, int ov_cap_j, int ov_cap_q,
+                               int64_t cap_ops, int64_t* out_info, int32_t* out_pod, int32_t* out_node,
+                               hipStream_t stm) {
+    if (cap < 1 || cap > kTopK || cap_ops < 1) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_walk_victims, dim3(1), dim3(kWalkBlock), 0, stm, st, h, head, cap, after_key, task, node_base,
+                       spill, spill_stride, ov_cap_j, ov_cap_q, cap_ops, out_info, out_pod, out_node);
+    return hipGetLastError();
 }
 
 hipError_t launch_head_victims(const VictState& st, const VictHdr& h, const uint64_t* head, int cap, int stride,

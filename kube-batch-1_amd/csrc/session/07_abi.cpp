@@ -162,6 +162,11 @@ int kbhip_set_option(kb_session* s, const char* key, int64_t value) {
             if (value < 0) throw kbhip::Error(KBHIP_EINVAL, "victims_dirty_max must not be negative");
             s->s.vs_dirty_max = value;
         }
+        else if (std::strcmp(key, "walk_overlay_max") == 0) {  // kbhip_walk_victims: touched jobs / queues carried (tests)
+            if (value < 0 || value > kbhip::kWalkOvJobs)
+                throw kbhip::Error(KBHIP_EINVAL, "walk_overlay_max must be 0 (full) .. " + std::to_string(kbhip::kWalkOvJobs));
+            s->s.walk_ov_max = (int32_t)value;
+        }
         else if (std::strcmp(key, "bf_batch") == 0) s->s.bf_batch = value != 0;
         else if (std::strcmp(key, "aff_batch") == 0) s->s.aff_batch = value != 0;
         else if (std::strcmp(key, "aff_fence") == 0) s->s.aff_fence = value != 0;

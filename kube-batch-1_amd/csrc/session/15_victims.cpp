@@ -1,10 +1,14 @@
 // kbhip session, part 15: the victim sets of a walk's head nodes (kbhip_head_victims), the victim state they
-// are read from, and the same decision on the host tables (kbhip_debug_victims)
+// are read from, one task's whole eviction walk over that head (kbhip_walk_victims), and the same decisions
+// on the host tables (kbhip_debug_victims, kbhip_debug_walk_victims)
 #include "framework.h"
 
 namespace kbhip {
 
 static_assert(KBHIP_HEAD_VICTIMS_VALID == 1 && KBHIP_HEAD_VICTIMS_COVERS == 2, "vict_decide's flag bits");
+static_assert(KBHIP_WALK_ASSIGNED == kWalkAssigned && KBHIP_WALK_EXHAUSTED == kWalkExhausted &&
+                  KBHIP_WALK_HEAD_END == kWalkHeadEnd && KBHIP_WALK_CAPACITY == kWalkCapacity,
+              "walk_step's stop reasons");
 
 struct Session::VictHost {  // the victim state on the host (VictState, kbhip_internal.h)
     vector<int32_t> node_off, pos;
@@ -201,6 +205,32 @@ VictHdr make_hdr(const Session& S, const HPod& p, int mode) {
     return h;
 }
 
+// What kbhip_head_victims and kbhip_walk_victims do before their own kernel: the plugins opened, the call's
+// header, both tables made current (built, or the dirty records patched in one launch) and the head sweep and
+// merge of kbhip_rank_victim_nodes enqueued — b_rank_head holds the head in stream order.
+struct HeadPrep {
+    VictHdr h;
+    bool rebuilt, vs_rebuilt;
+    int64_t patched, launches;
+};
+HeadPrep head_prepare(Session& S, const HPod& p, bool by_score, int mode) {
+    Framework F(S);
+    F.open_plugins();  // drf / proportion as OnSessionOpen leaves them (kbhip_apply_ops opens them the same way)
+    const VictHdr h = make_hdr(S, p, mode);
+    const bool vs_rebuilt = !S.vs_live;
+    if (!S.vict_live) vict_check_size(S);  // both tables' limits are checked before either is uploaded
+    if (vs_rebuilt) vs_build(S);           // (its own limit: after the host build, before the upload)
+    const bool rebuilt = vict_ensure(S);
+    int64_t launches = flush_tables(S);  // evictions / unevicts so far change pod-affinity predicates
+    const int64_t patched = vs_rebuilt ? 0 : vs_patch(S);
+    launches += patched ? 1 : 0;
+    vector<int32_t> own_node;
+    vector<int64_t> own_sum;
+    const VictArgs v = vict_args(S, p, mode, own_node, own_sum);
+    launches += rank_head_enqueue(S, p.cls, by_score, &v);
+    return HeadPrep{h, rebuilt, vs_rebuilt, patched, launches};
+}
+
 }  // namespace
 
 void vs_mark_dirty(Session& S, const int32_t* pod, int64_t n) {
@@ -230,20 +260,11 @@ int64_t head_victims_abi(Session& S, int pod, bool by_score, int mode, int cap, 
                          int32_t* out_victim, int64_t* out_info) {
     const HPod& p = query_task(S, pod, "kbhip_head_victims: the task ", true, "task id ");
     query_begin(S, "kbhip_head_victims");
-    Framework F(S);
-    F.open_plugins();  // drf / proportion as OnSessionOpen leaves them (kbhip_apply_ops opens them the same way)
-    const VictHdr h = make_hdr(S, p, mode);
-    const bool vs_rebuilt = !S.vs_live;
-    if (!S.vict_live) vict_check_size(S);  // both tables' limits are checked before either is uploaded
-    if (vs_rebuilt) vs_build(S);           // (its own limit: after the host build, before the upload)
-    const bool rebuilt = vict_ensure(S);
-    int64_t launches = flush_tables(S);  // evictions / unevicts so far change pod-affinity predicates
-    const int64_t patched = vs_rebuilt ? 0 : vs_patch(S);
-    launches += patched ? 1 : 0;
-    vector<int32_t> own_node;
-    vector<int64_t> own_sum;
-    const VictArgs v = vict_args(S, p, mode, own_node, own_sum);
-    launches += rank_head_enqueue(S, p.cls, by_score, &v);
+    const HeadPrep hp = head_prepare(S, p, by_score, mode);
+    const VictHdr& h = hp.h;
+    const bool rebuilt = hp.rebuilt, vs_rebuilt = hp.vs_rebuilt;
+    const int64_t patched = hp.patched;
+    int64_t launches = hp.launches;
     // the rows hold at most the longest node's tasks; a larger stride is filled with -1 here
     const int dstride = std::max(1, std::min(stride, S.vs_max_tasks));
     const size_t key_bytes = (size_t)(kTopK + 1) * sizeof(uint64_t),
@@ -309,6 +330,88 @@ void debug_victims(Session& S, int pod, int mode, int node, int stride, int32_t*
     *out_flags = (uint8_t)flags;
 }
 
+// One task's eviction walk over the head (kbhip_walk_victims): kbhip_head_victims' preparation, then
+// k_walk_victims on the merged keys — the node loop with the evictions of the earlier nodes carried in an
+// overlay inside the launch — one copy back, one wait.  Read-only as kbhip_head_victims is.
+int64_t walk_victims_abi(Session& S, int pod, bool by_score, int mode, int cap, int after_node, int after_score,
+                         uint8_t* out_op, int32_t* out_pod, int32_t* out_node, int64_t cap_ops, int64_t* out_info) {
+    const HPod& p = query_task(S, pod, "kbhip_walk_victims: the task ", true, "task id ");
+    if (after_node < -1 || after_node >= S.n_total)
+        throw Error(KBHIP_EINVAL, "kbhip_walk_victims: after_node is -1 or a node index");
+    query_begin(S, "kbhip_walk_victims");
+    const HeadPrep hp = head_prepare(S, p, by_score, mode);
+    // no walk writes more ops than the tasks of kTopK nodes (or of the state) and one pipeline
+    const int64_t most = std::min<int64_t>((int64_t)kTopK * S.vs_max_tasks, S.vs_tasks) + 1,
+                  dcap = std::min(cap_ops, most);
+    const size_t info_bytes = 8 * sizeof(int64_t), out_bytes = info_bytes + (size_t)dcap * 2 * sizeof(int32_t);
+    S.h_vs_out.fit(out_bytes, std::max<size_t>(out_bytes, 4096));
+    S.b_vs_out.grow(S.stream, out_bytes, std::max<size_t>(out_bytes, 4096));
+    uint8_t* const d_out = (uint8_t*)S.b_vs_out.p;
+    const uint64_t after_key = after_node < 0 ? 0 : pack_key(by_score ? after_score : 0, after_node, 0);
+    const bool spill = S.vs_max_tasks > kVictLds;
+    const int ov = S.walk_ov_max;
+    HIPCHK(launch_walk_victims(vs_device_view(S), hp.h, (const uint64_t*)S.b_rank_head.p, cap, after_key, pod,
+                               S.nc.base, spill ? (VictRec*)S.b_vs_spill.p : nullptr, spill ? S.vs_max_tasks : 0,
+                               ov > 0 ? ov : kWalkOvJobs, ov > 0 ? ov : kWalkOvQueues, dcap, (int64_t*)d_out,
+                               (int32_t*)(d_out + info_bytes), (int32_t*)(d_out + info_bytes) + dcap, S.stream));
+    HIPCHK(hipMemcpyAsync(S.h_vs_out.p, d_out, out_bytes, hipMemcpyDeviceToHost, S.stream));
+    HIPCHK(hipStreamSynchronize(S.stream));
+    const int64_t* info = S.h_vs_out.as<int64_t>();
+    const int32_t* pods = (const int32_t*)(S.h_vs_out.as<uint8_t>() + info_bytes);
+    const int64_t n = std::min(std::max<int64_t>(info[6], 0), dcap);
+    std::memcpy(out_pod, pods, (size_t)n * sizeof(int32_t));
+    std::memcpy(out_node, pods + dcap, (size_t)n * sizeof(int32_t));
+    std::fill(out_op, out_op + n, (uint8_t)KBHIP_OP_EVICT);
+    if (info[0] == KBHIP_WALK_ASSIGNED && n > 0) out_op[n - 1] = KBHIP_OP_PIPELINE;
+    if (out_info) {
+        for (int k = 0; k < 6; ++k) out_info[k] = info[k];
+        if (!by_score) out_info[5] = 0;
+        out_info[6] = hp.launches + 1;
+        out_info[7] = (hp.rebuilt ? 1 : 0) | (hp.vs_rebuilt ? 2 : 0) | (hp.patched << 8);
+    }
+    S.stats.sweeps++;
+    return n;
+}
+
+// The same walk over a caller's node list from the host tables of an encode-only session: the state built
+// on the host, then per node vict_stage_walk / vict_link / walk_step, the functions the kernel runs.
+int64_t debug_walk_victims(Session& S, int pod, int mode, const int32_t* nodes, int n_nodes, int64_t cap_ops,
+                           uint8_t* out_op, int32_t* out_pod, int32_t* out_node, int64_t* out_info) {
+    const HPod& p = query_task(S, pod, "kbhip_debug_walk_victims: the task ", true, "task id ");
+    for (int i = 0; i < n_nodes; ++i)
+        if (nodes[i] < 0 || nodes[i] >= S.n_total)
+            throw Error(KBHIP_EINVAL, "kbhip_debug_walk_victims: node index out of range");
+    Framework F(S);
+    F.open_plugins();
+    Session::VictHost H;
+    vs_build_host(S, H);
+    VictHdr h = make_hdr(S, p, mode);
+    const VictState st = H.view(S);
+    const int64_t dcap = std::min<int64_t>(cap_ops, (int64_t)H.task.size() + 1);
+    vector<int32_t> pods((size_t)dcap), onto((size_t)dcap);
+    vector<VictRec> rec(std::max(H.max_tasks, 1));
+    WalkOverlay ov;
+    const int ovm = S.walk_ov_max;
+    walk_ov_init(ov, ovm > 0 ? ovm : kWalkOvJobs, ovm > 0 ? ovm : kWalkOvQueues);
+    WalkCtl c{0, dcap, 0, 0, 0, -1, 0, pod};
+    for (int i = 0; i < n_nodes && c.stop == 0; ++i) {
+        const int off = st.node_off[nodes[i]], n = st.node_off[nodes[i] + 1] - off;
+        for (int k = 0; k < n; ++k) vict_stage_walk(st, h, ov, off + k, rec[k]);
+        for (int k = 0; k < n; ++k) vict_link(rec.data(), k);
+        walk_step(h, ov, c, rec.data(), n, nodes[i], 0, pods.data(), onto.data());
+    }
+    const int64_t n = c.n_ops;
+    std::copy(pods.begin(), pods.begin() + n, out_pod);
+    std::copy(onto.begin(), onto.begin() + n, out_node);
+    std::fill(out_op, out_op + n, (uint8_t)KBHIP_OP_EVICT);
+    if (c.stop == kWalkAssigned) out_op[n - 1] = KBHIP_OP_PIPELINE;
+    if (out_info) {
+        const int64_t v[8] = {c.stop ? c.stop : kWalkExhausted, n_nodes, c.visited, c.acted, c.last_node, 0, 0, 0};
+        std::copy(v, v + 8, out_info);
+    }
+    return n;
+}
+
 // kbhip_debug_table's views of the plugin state the victim functions read (drf / proportion opened first)
 bool debug_victim_table(Session& S, const string& name, vector<uint8_t>& out) {
     auto put = [&out](const auto* src, size_t n) {
@@ -371,6 +474,39 @@ int64_t kbhip_head_victims(kb_session* s, int32_t task_id, int32_t by_score, int
             throw kbhip::Error(KBHIP_EINVAL, "kbhip_head_victims: victims is one of KBHIP_VICTIMS_* (1..3)");
         return kbhip::head_victims_abi(kbhip::device_session(s), task_id, by_score != 0, victims, cap, stride,
                                        out_node, out_score, out_count, out_evict, out_flags, out_victim, out_info);
+    })
+}
+
+int64_t kbhip_walk_victims(kb_session* s, int32_t task_id, int32_t by_score, int32_t victims, int32_t cap,
+                           int32_t after_node, int32_t after_score, uint8_t* out_op, int32_t* out_pod,
+                           int32_t* out_node, int64_t cap_ops, int64_t* out_info) {
+    ABI_GUARD_S(s, {
+        if (cap < 1 || cap > 64) throw kbhip::Error(KBHIP_EINVAL, "kbhip_walk_victims: cap is 1 .. 64");
+        if (cap_ops < 1) throw kbhip::Error(KBHIP_EINVAL, "kbhip_walk_victims: cap_ops is at least 1");
+        if (!out_op || !out_pod || !out_node)
+            throw kbhip::Error(KBHIP_EINVAL, "kbhip_walk_victims: null out_op, out_pod or out_node");
+        if (by_score != 0 && by_score != 1) throw kbhip::Error(KBHIP_EINVAL, "kbhip_walk_victims: by_score is 0 or 1");
+        if (victims < KBHIP_VICTIMS_OTHER_QUEUES || victims > KBHIP_VICTIMS_SAME_JOB)
+            throw kbhip::Error(KBHIP_EINVAL, "kbhip_walk_victims: victims is one of KBHIP_VICTIMS_* (1..3)");
+        return kbhip::walk_victims_abi(kbhip::device_session(s), task_id, by_score != 0, victims, cap, after_node,
+                                       after_score, out_op, out_pod, out_node, cap_ops, out_info);
+    })
+}
+
+int64_t kbhip_debug_walk_victims(kb_session* s, int32_t task_id, int32_t victims, const int32_t* nodes,
+                                 int32_t n_nodes, int64_t cap_ops, uint8_t* out_op, int32_t* out_pod,
+                                 int32_t* out_node, int64_t* out_info) {
+    ABI_GUARD({
+        if (!s || !out_op || !out_pod || !out_node || (n_nodes > 0 && !nodes))
+            throw kbhip::Error(KBHIP_EINVAL, "null argument");
+        if (!s->s.encode_only)
+            throw kbhip::Error(KBHIP_EINVAL, "kbhip_debug_walk_victims needs an encode-only session");
+        if (n_nodes < 0) throw kbhip::Error(KBHIP_EINVAL, "kbhip_debug_walk_victims: negative n_nodes");
+        if (cap_ops < 1) throw kbhip::Error(KBHIP_EINVAL, "kbhip_debug_walk_victims: cap_ops is at least 1");
+        if (victims < KBHIP_VICTIMS_OTHER_QUEUES || victims > KBHIP_VICTIMS_SAME_JOB)
+            throw kbhip::Error(KBHIP_EINVAL, "kbhip_debug_walk_victims: victims is one of KBHIP_VICTIMS_* (1..3)");
+        return kbhip::debug_walk_victims(s->s, task_id, victims, nodes, n_nodes, cap_ops, out_op, out_pod, out_node,
+                                         out_info);
     })
 }
 

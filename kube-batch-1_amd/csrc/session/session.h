@@ -630,6 +630,9 @@ struct Session {
     DevBuf b_vs_off, b_vs_task, b_vs_job, b_vs_queue, b_vs_spill, b_vs_patch, b_vs_out;
     PinnedBuf h_vs_patch, h_vs_out;
     struct VictHost;  // the state on the host (15_victims.cpp)
+    // kbhip_walk_victims: option "walk_overlay_max" (tests; 0 = the full overlay): the touched jobs and the
+    // touched queues a walk carries at most
+    int32_t walk_ov_max = 0;
     // kbhip_rank_heads (13_heads.cpp).  h_heads_in / b_heads_in: one call's upload — a PopCtrl image
     // of the call's own (slot i: request i's class, inter-pod min / max zero), its HeadDescs, the own-job
     // lists of its jobs; b_heads: the kernels' scratch (rank_heads_words); h_heads_out: kMaxChunk
@@ -1274,6 +1277,12 @@ void vs_mark_dirty(Session& S, const int32_t* pod, int64_t n);
 void debug_victims(Session& S, int pod, int mode, int node, int stride, int32_t* out_count, int32_t* out_evict,
                    uint8_t* out_flags, int32_t* out_victim);
 bool debug_victim_table(Session& S, const string& name, vector<uint8_t>& out);
+// kbhip_walk_victims / kbhip_debug_walk_victims (15_victims.cpp): one task's eviction walk, on the head and
+// over a caller's node list on the host tables
+int64_t walk_victims_abi(Session& S, int pod, bool by_score, int mode, int cap, int after_node, int after_score,
+                         uint8_t* out_op, int32_t* out_pod, int32_t* out_node, int64_t cap_ops, int64_t* out_info);
+int64_t debug_walk_victims(Session& S, int pod, int mode, const int32_t* nodes, int n_nodes, int64_t cap_ops,
+                           uint8_t* out_op, int32_t* out_pod, int32_t* out_node, int64_t* out_info);
 // The head path of rank_victim_nodes_abi, shared with kbhip_head_victims.  vict_args: the job's own list
 // uploaded and the call's VictArgs.  rank_head_enqueue: the control block, the inter-pod prepass where the
 // class has one, the sweep and the merge on the session's stream (b_rank_head holds the result once they

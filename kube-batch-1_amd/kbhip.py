@@ -24,6 +24,14 @@ OP_EVICT, OP_PIPELINE, OP_UNPIPELINE, OP_UNEVICT = 1, 2, 3, 4  # kbhip_apply_ops
 VICTIMS_OTHER_QUEUES, VICTIMS_QUEUE_OTHER_JOBS, VICTIMS_SAME_JOB = 1, 2, 3  # kbhip_rank_victim_nodes
 RANK_HEADS_MAX = 64  # KBHIP_RANK_HEADS_MAX: tasks per kbhip_rank_heads
 HEAD_VICTIMS_VALID, HEAD_VICTIMS_COVERS = 1, 2  # kbhip_head_victims: out_flags bits
+WALK_ASSIGNED, WALK_EXHAUSTED, WALK_HEAD_END, WALK_CAPACITY = 1, 2, 3, 4  # kbhip_walk_victims: stop reasons
+_WALK_INFO = ("stop", "total", "visited", "acted", "last_node", "last_score", "launches")
+
+
+def _walk_info(info):
+    d = dict(zip(_WALK_INFO, map(int, info[:7])))
+    d.update(rebuilt=int(info[7]) & 1, state_rebuilt=(int(info[7]) >> 1) & 1, patched=int(info[7]) >> 8)
+    return d
 # kbhip_explain_tasks: the verdict codes (low four bits of a verdict byte), the short bits of codes 0..2
 (WHY_FITS_IDLE, WHY_FITS_RELEASING, WHY_RESOURCES, WHY_POD_COUNT, WHY_NODE_SELECTOR, WHY_HOST_PORTS,
  WHY_UNSCHEDULABLE, WHY_TAINTS, WHY_POD_AFFINITY, WHY_SCORE_ERROR) = range(10)
@@ -42,7 +50,8 @@ EXPORTS = ("kbhip_device_count", "kbhip_session_open", "kbhip_session_open_file"
            "kbhip_place_job_wait", "kbhip_place_job_cancel", "kbhip_time_sweeps", "kbhip_time_rank_multi",
            "kbhip_session_carry_snapshot", "kbhip_walk_visits", "kbhip_fit_deltas", "kbhip_rank_nodes",
            "kbhip_apply_ops", "kbhip_rank_victim_nodes", "kbhip_rank_heads", "kbhip_explain_tasks",
-           "kbhip_debug_explain", "kbhip_head_victims", "kbhip_debug_victims")
+           "kbhip_debug_explain", "kbhip_head_victims", "kbhip_debug_victims", "kbhip_walk_victims",
+           "kbhip_debug_walk_victims")
 
 RED_MAX_U64, RED_MIN_I64, RED_MAX_I64, RED_SUM_I64 = 0, 1, 2, 3
 ALLREDUCE_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint64), ctypes.c_int32,
@@ -154,6 +163,10 @@ def lib() -> ctypes.CDLL:
         L.kbhip_head_victims.argtypes = [vp, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp]
         L.kbhip_head_victims.restype = i64
         L.kbhip_debug_victims.argtypes = [vp, i32, i32, i32, i32, vp, vp, vp, vp]
+        L.kbhip_walk_victims.argtypes = [vp, i32, i32, i32, i32, i32, i32, vp, vp, vp, i64, vp]
+        L.kbhip_walk_victims.restype = i64
+        L.kbhip_debug_walk_victims.argtypes = [vp, i32, i32, vp, i32, i64, vp, vp, vp, vp]
+        L.kbhip_debug_walk_victims.restype = i64
         _lib = L
     return _lib
 
@@ -346,6 +359,25 @@ class Session:
         return (n, node[:cap], score[:cap], count[:cap], evict[:cap], flags[:cap],
                 victim[: cap * stride].reshape(cap, stride),
                 dict(zip(("rebuilt", "state_rebuilt", "patched", "launches", "max_count"), map(int, info))))
+
+    def walk_victims(self, task_id: int, by_score: bool = True, victims: int = VICTIMS_OTHER_QUEUES,
+                     cap: int = 64, after=None, cap_ops: int = 4096):
+        """kbhip_walk_victims: the task's whole eviction walk over the head of
+        its pruned walk, the evictions of each node carried to the next:
+        (ops[n], pods[n], nodes[n], info), ready for apply_ops.  after: None,
+        or (node, score) of the last acted-on node of the call to resume.
+        info: {"stop" (a WALK_* reason), "total", "visited", "acted",
+        "last_node", "last_score", "launches", "rebuilt", "state_rebuilt",
+        "patched"}."""
+        cap_ops = int(cap_ops)
+        room = max(cap_ops, 1)
+        op, pod, node = np.zeros(room, np.uint8), np.full(room, -1, np.int32), np.full(room, -1, np.int32)
+        info = np.zeros(8, np.int64)
+        a_node, a_score = (-1, 0) if after is None else (int(after[0]), int(after[1]))
+        n = int(lib().kbhip_walk_victims(self._h, int(task_id), int(by_score), int(victims), int(cap), a_node, a_score,
+                                         _p(op), _p(pod), _p(node), cap_ops, _p(info)))
+        _check(n if n < 0 else 0)
+        return op[:n].copy(), pod[:n].copy(), node[:n].copy(), _walk_info(info)
 
     def explain_tasks(self, task_ids, verdicts: bool = False, n_nodes: Optional[int] = None):
         """kbhip_explain_tasks: why each node is, or is not, in the allocate
@@ -639,6 +671,23 @@ class EncodedSnapshot:
         _check(lib().kbhip_debug_victims(self._h, int(task_id), int(victims), int(node), int(stride), _p(count),
                                          _p(evict), _p(flags), _p(row)))
         return int(count[0]), int(evict[0]), int(flags[0]), row[: min(int(count[0]), int(stride))].copy()
+
+    def walk_victims(self, task_id: int, victims: int, nodes, cap_ops: int = 4096):
+        """kbhip_debug_walk_victims: kbhip_walk_victims' node loop over `nodes`
+        in the given order, by the kernel's own functions on the host tables:
+        (ops[n], pods[n], nodes[n], info) as Session.walk_victims."""
+        nd = np.ascontiguousarray(nodes, dtype=np.int32).reshape(-1)
+        cap_ops = int(cap_ops)
+        room = max(cap_ops, 1)
+        op, pod, node = np.zeros(room, np.uint8), np.full(room, -1, np.int32), np.full(room, -1, np.int32)
+        info = np.zeros(8, np.int64)
+        n = int(lib().kbhip_debug_walk_victims(self._h, int(task_id), int(victims), _p(nd) if nd.size else None,
+                                               int(nd.size), cap_ops, _p(op), _p(pod), _p(node), _p(info)))
+        _check(n if n < 0 else 0)
+        return op[:n].copy(), pod[:n].copy(), node[:n].copy(), _walk_info(info)
+
+    def set_option(self, key: str, value: int) -> None:
+        _check(lib().kbhip_set_option(self._h, key.encode(), int(value)))
 
     def replay(self, pods, modes, nodes, kinds) -> np.ndarray:
         """Per-step, per-node selection keys along a given decision sequence
