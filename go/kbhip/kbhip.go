@@ -428,6 +428,79 @@ func (e *Engine) HeadVictims(task int32, byScore bool, victims int32, cap, strid
 	return int64(t), heads, info, nil
 }
 
+// HeadsVictimsMax is the most tasks one HeadsVictims call answers (KBHIP_HEADS_VICTIMS_MAX).
+const HeadsVictimsMax = int(C.KBHIP_HEADS_VICTIMS_MAX)
+
+// TaskHeadVictims is one task's answer of HeadsVictims: what HeadVictims
+// returns for it, and First, the index in Heads of the first entry with
+// HeadVictimsValid (-1: the task acts on none of its head nodes).
+type TaskHeadVictims struct {
+	Total int64
+	First int32
+	Heads []HeadVictim
+}
+
+// HeadsVictimsInfo says what a HeadsVictims call did (out_info of kbhip_heads_victims).
+type HeadsVictimsInfo struct {
+	HeadVictimsInfo
+	VictimLaunches int64 // the victims launches among Launches: 1 unless the spill bound split the batch
+}
+
+// HeadsVictims answers HeadVictims for up to HeadsVictimsMax Pending tasks in
+// one call (kbhip_heads_victims): out[i] is what HeadVictims(tasks[i], byScore,
+// victims, cap, stride) returns on the session as it stands.  Every task is
+// answered against the session at the call — no eviction is carried from one
+// task to the next.  A host that prefetches uses the answers up to the first
+// task it acts on and discards the rest once an ApplyOps is sent; First lets it
+// pass over the tasks that act on no node.  A task may appear more than once.
+func (e *Engine) HeadsVictims(tasks []int32, byScore bool, victims int32, cap, stride int) (out []TaskHeadVictims, info HeadsVictimsInfo, err error) {
+	if len(tasks) == 0 { // &tasks[0] of an empty slice panics
+		return nil, info, nil
+	}
+	if len(tasks) > HeadsVictimsMax || cap < 1 || cap > 64 || stride < 1 {
+		return nil, info, fmt.Errorf("kbhip heads_victims: %d tasks (1..%d), cap %d (1..64), stride %d (>= 1)",
+			len(tasks), HeadsVictimsMax, cap, stride)
+	}
+	n := len(tasks)
+	total := make([]int64, n)
+	nodes, scores := make([]int32, n*cap), make([]int32, n*cap)
+	counts, evicts := make([]int32, n*cap), make([]int32, n*cap)
+	flags := make([]uint8, n*cap)
+	rows := make([]int32, n*cap*stride)
+	first := make([]int32, n)
+	var raw [6]C.int64_t
+	if r := C.kbhip_heads_victims(e.s, (*C.int32_t)(unsafe.Pointer(&tasks[0])), C.int32_t(n), boolI32(byScore),
+		C.int32_t(victims), C.int32_t(cap), C.int32_t(stride), (*C.int64_t)(unsafe.Pointer(&total[0])),
+		(*C.int32_t)(unsafe.Pointer(&nodes[0])), (*C.int32_t)(unsafe.Pointer(&scores[0])),
+		(*C.int32_t)(unsafe.Pointer(&counts[0])), (*C.int32_t)(unsafe.Pointer(&evicts[0])),
+		(*C.uint8_t)(unsafe.Pointer(&flags[0])), (*C.int32_t)(unsafe.Pointer(&rows[0])),
+		(*C.int32_t)(unsafe.Pointer(&first[0])), &raw[0]); r < 0 {
+		return nil, info, lastErr("heads_victims", C.int(r))
+	}
+	info = HeadsVictimsInfo{HeadVictimsInfo: HeadVictimsInfo{Rebuilt: raw[0] != 0, StateRebuilt: raw[1] != 0,
+		Patched: int64(raw[2]), Launches: int64(raw[3]), MaxCount: int64(raw[4])}, VictimLaunches: int64(raw[5])}
+	out = make([]TaskHeadVictims, n)
+	for t := range out {
+		k := int64(cap)
+		if total[t] < k {
+			k = total[t]
+		}
+		heads := make([]HeadVictim, k)
+		for i := range heads {
+			at := t*cap + i
+			c := int(counts[at])
+			if c > stride {
+				c = stride
+			}
+			lo := at * stride
+			heads[i] = HeadVictim{Node: nodes[at], Score: scores[at], Count: counts[at], Evict: evicts[at],
+				Flags: flags[at], Victims: rows[lo : lo+c : lo+c]}
+		}
+		out[t] = TaskHeadVictims{Total: total[t], First: first[t], Heads: heads}
+	}
+	return out, info, nil
+}
+
 // The stop reasons of WalkVictims (KBHIP_WALK_*).
 const (
 	WalkAssigned  = int(C.KBHIP_WALK_ASSIGNED)  // a node covered InitResreq: the last op pipelines the task

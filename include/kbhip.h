@@ -444,6 +444,64 @@ int64_t kbhip_head_victims(kb_session* s, int32_t task_id, int32_t by_score, int
                            int32_t* out_evict, uint8_t* out_flags, int32_t* out_victim /* cap rows of stride */,
                            int64_t* out_info /* optional */);
 
+/* kbhip_heads_victims <- kbhip_head_victims for up to KBHIP_HEADS_VICTIMS_MAX
+ * tasks in one call: the call's fixed cost (upload, launches, copy, wait) paid
+ * once per batch.  A host forms the batch where kbhip_rank_heads names one —
+ * task after task asked with no operation in between, as reclaim's and
+ * preempt's loops do for the many pending tasks that act on no node.
+ * For task_ids[i], out_total[i], row i of out_node, out_score (optional),
+ * out_count, out_evict and out_flags (n_tasks rows of cap entries) and rows
+ * i * cap .. i * cap + cap - 1 of out_victim (stride entries each) hold exactly
+ * what kbhip_head_victims(task_ids[i], by_score, victims, cap, stride, ..)
+ * returns and writes on the session as it stands, the -1 / 0 entries beyond
+ * min(cap, total) and the -1 tail of each victim row included: the call
+ * defines its whole output.  out_first[i] (optional, n_tasks entries) is the
+ * index of task i's first head entry with KBHIP_HEAD_VICTIMS_VALID, or -1: the
+ * one word a host reads to pass over a task that acts on no node.
+ * Every row is answered against the session at the call, with no evictions
+ * carried from one task, or one node, to the next: kbhip_head_victims'
+ * semantics, not kbhip_walk_victims'.  A host that prefetches uses the rows up
+ * to the first task it acts on and discards the rest at its next
+ * kbhip_apply_ops.
+ * A task may appear more than once; tasks of different classes, jobs and
+ * queues, pod-affinity classes and classes with inter-pod priority terms mix
+ * freely, as in kbhip_rank_heads.  by_score, victims, cap and stride hold for
+ * the whole batch.  Returns n_tasks (0 for n_tasks == 0, which does nothing).
+ * out_info (optional, 6 entries): [0] whether the candidate table was rebuilt,
+ * [1] whether the victim state was rebuilt, [2] the records patched into it,
+ * [3] the kernel launches, [4] the largest out_count of the batch, [5] the
+ * victims launches among them.
+ * Launches: what kbhip_rank_heads issues for the batch in a victims mode, one
+ * patch launch when dirty records were waiting, then the victims launch — one
+ * for the batch; only where a node holds more than 256 candidate tasks do the
+ * blocks stage into device memory, n_tasks * cap rows of the longest node's
+ * length, and a batch whose rows exceed option "victims_spill_max" (bytes,
+ * default 256 MB) runs as consecutive ranges of tasks that each fit, one launch
+ * per range.  One upload from pinned staging (the control image, the
+ * descriptors, the own-job lists and the tasks' victim headers), one copy
+ * back, one wait.
+ * The call changes the currency of the candidate table and of the victim
+ * state and the plugins' open state, and nothing else: no node row, no counter
+ * of kbhip_walk_visits, and a task kbhip_fit_deltas would answer for stays
+ * answerable.  kbhip_stats.sweeps and kbhip_stats.rank_heads count one per
+ * answered task.  The whole batch is validated before any device work, and a
+ * refused call writes nothing.  KBHIP_EINVAL: a null session, task_ids,
+ * out_total, out_node, out_count, out_evict, out_flags or out_victim; n_tasks
+ * outside 0 .. 64, cap outside 1 .. 64, stride < 1, by_score not 0 or 1,
+ * victims outside 1 .. 3; a task without a class, not Pending or without a job
+ * (the message names the index in task_ids); an encode-only session; submitted
+ * pops outstanding.  KBHIP_EUNSUPPORTED: where kbhip_head_victims and
+ * kbhip_rank_heads refuse; the cap staging rows of one task above
+ * "victims_spill_max" (the message names the size). */
+#define KBHIP_HEADS_VICTIMS_MAX 64
+int64_t kbhip_heads_victims(kb_session* s, const int32_t* task_ids, int32_t n_tasks, int32_t by_score,
+                            int32_t victims /* KBHIP_VICTIMS_* 1..3 */, int32_t cap /* 1..64 */,
+                            int32_t stride /* >= 1 */, int64_t* out_total /* n_tasks */,
+                            int32_t* out_node /* n_tasks rows of cap */, int32_t* out_score /* optional */,
+                            int32_t* out_count, int32_t* out_evict, uint8_t* out_flags /* n_tasks rows of cap */,
+                            int32_t* out_victim /* n_tasks * cap rows of stride */,
+                            int32_t* out_first /* optional, n_tasks */, int64_t* out_info /* optional, 6 */);
+
 /* kbhip_walk_victims <- one task's whole node loop of preempt()
  * (preempt.go:259-353) or of reclaim (reclaim.go:115-189) over the head of its
  * pruned walk, in one call: the finished batch for kbhip_apply_ops.

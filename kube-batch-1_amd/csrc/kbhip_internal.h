@@ -266,6 +266,14 @@ constexpr int kVictLds = 256;  // node tasks a block stages in LDS; larger nodes
 hipError_t launch_head_victims(const VictState& st, const VictHdr& h, const uint64_t* head, int cap, int stride,
                                int node_base, VictRec* spill, int spill_stride, uint64_t* out_keys, int32_t* out,
                                hipStream_t stm);
+// kbhip_heads_victims: the same rows for n_req (1 .. kMaxChunk) requests in one launch, grid (cap, n_req).
+// Request r's head is heads[r (kTopK + 1) ..] (launch_rank_heads' result), its header hdr[r] (device
+// memory).  out_keys: n_req results of kTopK + 1 words; out: n_req * cap rows as above, request-major.
+// lds_recs (1 .. kVictLds): the records a block stages in dynamic LDS, at least min(kVictLds, the largest
+// node of the state).  spill: n_req * cap rows of spill_stride records, or null when no node is longer.
+hipError_t launch_heads_victims(const VictState& st, const VictHdr* hdr, const uint64_t* heads, int n_req, int cap,
+                                int stride, int node_base, int lds_recs, VictRec* spill, int spill_stride,
+                                uint64_t* out_keys, int32_t* out, hipStream_t stm);
 // The records kbhip_apply_ops left dirty, scattered into the state: task[t_pos[i]].flags = t_flags[i],
 // job[j_id[i]] = j_rec[i], queue[q_id[i]] = q_rec[i] (device pointers; indices distinct within each list).
 struct VictPatch {

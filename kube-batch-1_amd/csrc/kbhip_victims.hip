@@ -22,6 +22,12 @@
 //                    function.  The lanes fill the victim row's tail with -1.
 //                    Block 0 also copies the head's keys and count, so that
 //                    one copy back returns everything.
+//   k_heads_victims  kbhip_heads_victims: the same rows (one shared device
+//                    function) for up to kMaxChunk tasks in one launch, grid
+//                    (cap, requests): block (i, r) reads request r's head where
+//                    k_rank_heads_merge left it and its header from a device
+//                    array; the staged records take dynamic LDS sized by the
+//                    state's longest node.
 //   k_walk_victims   kbhip_walk_victims: one block walks the head entries in
 //                    order, staging each node as above under an overlay of
 //                    the evictions of the entries before it (described at the
@@ -35,28 +41,25 @@
 
 namespace kbhip {
 
-__global__ __launch_bounds__(64) void k_head_victims(VictState st, VictHdr h, const uint64_t* head, int cap, int stride,
-                                                     int node_base, VictRec* spill, int spill_stride,
-                                                     uint64_t* out_keys, int32_t* out) {
-    __shared__ VictRec s_rec[kVictLds];
-    const int i = blockIdx.x, lane = threadIdx.x;
-    if (i >= cap) return;
-    if (i == 0) {
-        out_keys[lane] = head[lane];
-        if (lane == 0) out_keys[kTopK] = head[kTopK];
-    }
-    int32_t* const row = out + (size_t)i * (3 + stride);
+// Head entry i of `head` (the keys, then the count) decided into `row` (count, evict, flags, then stride
+// victims), by one wave: what k_head_victims and k_heads_victims run per block.  lds: room for lds_cap
+// staged records; a longer node stages into spill_row (spill_stride records, or null).  An entry at or
+// beyond the head's count, or without a node, writes 0 / -1 and reads nothing of the state.
+__device__ __forceinline__ void head_victims_row(const VictState& st, const VictHdr& h, const uint64_t* head, int i,
+                                                 int stride, int node_base, VictRec* lds, int lds_cap,
+                                                 VictRec* spill_row, int spill_stride, int32_t* row) {
+    const int lane = threadIdx.x;
     const uint64_t key = head[i], total = head[kTopK];
     const int node = key_idx(key) - node_base;
     int off = 0, n = -1;  // n < 0: no node in this row
     if ((uint64_t)i < total && key != 0 && node >= 0 && node < st.n_nodes) {
         off = st.node_off[node];
         n = st.node_off[node + 1] - off;
-        if (off < 0 || n < 0 || off + n > st.n_tasks || (n > kVictLds && (!spill || n > spill_stride))) n = -1;
+        if (off < 0 || n < 0 || off + n > st.n_tasks || (n > lds_cap && (!spill_row || n > spill_stride))) n = -1;
     }
     int count = 0;
     if (n > 0) {  // (uniform over the block)
-        VictRec* const rec = n <= kVictLds ? s_rec : spill + (size_t)i * spill_stride;
+        VictRec* const rec = n <= lds_cap ? lds : spill_row;
         for (int k = lane; k < n; k += 64) vict_stage(st, h, off + k, rec[k]);
         __syncthreads();
         for (int k = lane; k < n; k += 64) vict_link(rec, k);
@@ -73,6 +76,43 @@ __global__ __launch_bounds__(64) void k_head_victims(VictState st, VictHdr h, co
         row[0] = row[1] = row[2] = 0;
     }
     for (int k = (count < stride ? count : stride) + lane; k < stride; k += 64) row[3 + k] = -1;
+}
+
+__global__ __launch_bounds__(64) void k_head_victims(VictState st, VictHdr h, const uint64_t* head, int cap, int stride,
+                                                     int node_base, VictRec* spill, int spill_stride,
+                                                     uint64_t* out_keys, int32_t* out) {
+    __shared__ VictRec s_rec[kVictLds];
+    const int i = blockIdx.x, lane = threadIdx.x;
+    if (i >= cap) return;
+    if (i == 0) {
+        out_keys[lane] = head[lane];
+        if (lane == 0) out_keys[kTopK] = head[kTopK];
+    }
+    head_victims_row(st, h, head, i, stride, node_base, s_rec, kVictLds,
+                     spill ? spill + (size_t)i * spill_stride : nullptr, spill_stride,
+                     out + (size_t)i * (3 + stride));
+}
+
+// kbhip_heads_victims: the same rows for n_req requests, grid (cap, n_req), blockIdx.y = the request.  Block
+// (i, r) reads request r's head where k_rank_heads_merge left it and its header from hdr[r]; the staged
+// records live in lds_recs records of dynamic LDS — min(kVictLds, the state's longest node), so that
+// sessions of small nodes keep a CU's 32 one-wave blocks resident where the static 43 KB allow three.
+extern __shared__ VictRec s_dyn_rec[];
+__global__ __launch_bounds__(64) void k_heads_victims(VictState st, const VictHdr* __restrict__ hdr,
+                                                      const uint64_t* __restrict__ heads, int cap, int stride,
+                                                      int node_base, int lds_recs, VictRec* spill, int spill_stride,
+                                                      uint64_t* out_keys, int32_t* out) {
+    const int i = blockIdx.x, r = blockIdx.y, lane = threadIdx.x;
+    if (i >= cap) return;
+    const uint64_t* const head = heads + (size_t)r * (kTopK + 1);
+    if (i == 0) {
+        uint64_t* const keys = out_keys + (size_t)r * (kTopK + 1);
+        keys[lane] = head[lane];
+        if (lane == 0) keys[kTopK] = head[kTopK];
+    }
+    const size_t at = (size_t)r * cap + i;
+    head_victims_row(st, hdr[r], head, i, stride, node_base, s_dyn_rec, lds_recs,
+                     spill ? spill + at * spill_stride : nullptr, spill_stride, out + at * (3 + stride));
 }
 
 __global__ __launch_bounds__(256) void k_victims_patch(VictTask* task, VictJob* job, VictQueue* queue, int n_tasks,
@@ -172,6 +212,16 @@ hipError_t launch_head_victims(const VictState& st, const VictHdr& h, const uint
     if (cap < 1 || cap > kTopK || stride < 1) return hipErrorInvalidValue;
     hipLaunchKernelGGL(k_head_victims, dim3(cap), dim3(64), 0, stm, st, h, head, cap, stride, node_base, spill,
                        spill_stride, out_keys, out);
+    return hipGetLastError();
+}
+
+hipError_t launch_heads_victims(const VictState& st, const VictHdr* hdr, const uint64_t* heads, int n_req, int cap,
+                                int stride, int node_base, int lds_recs, VictRec* spill, int spill_stride,
+                                uint64_t* out_keys, int32_t* out, hipStream_t stm) {
+    if (n_req < 1 || n_req > kMaxChunk || cap < 1 || cap > kTopK || stride < 1 || lds_recs < 1 || lds_recs > kVictLds)
+        return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_heads_victims, dim3(cap, n_req), dim3(64), (size_t)lds_recs * sizeof(VictRec), stm, st, hdr,
+                       heads, cap, stride, node_base, lds_recs, spill, spill_stride, out_keys, out);
     return hipGetLastError();
 }
 

@@ -162,6 +162,10 @@ int kbhip_set_option(kb_session* s, const char* key, int64_t value) {
             if (value < 0) throw kbhip::Error(KBHIP_EINVAL, "victims_dirty_max must not be negative");
             s->s.vs_dirty_max = value;
         }
+        else if (std::strcmp(key, "victims_spill_max") == 0) {  // kbhip_heads_victims: spill bytes of one victims launch
+            if (value < 1) throw kbhip::Error(KBHIP_EINVAL, "victims_spill_max must be at least 1");
+            s->s.vs_spill_max = value;
+        }
         else if (std::strcmp(key, "walk_overlay_max") == 0) {  // kbhip_walk_victims: touched jobs / queues carried (tests)
             if (value < 0 || value > kbhip::kWalkOvJobs)
                 throw kbhip::Error(KBHIP_EINVAL, "walk_overlay_max must be 0 (full) .. " + std::to_string(kbhip::kWalkOvJobs));

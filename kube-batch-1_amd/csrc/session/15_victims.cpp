@@ -92,14 +92,30 @@ size_t vs_bytes_of(const Session::VictHost& H) {
            H.queue.size() * sizeof(VictQueue);
 }
 
+}  // namespace
+
 VictState vs_device_view(const Session& S) {
     return VictState{(const int32_t*)S.b_vs_off.p, (const VictTask*)S.b_vs_task.p, (const VictJob*)S.b_vs_job.p,
                      (const VictQueue*)S.b_vs_queue.p, S.n_total, (int32_t)S.jobs.size(), (int32_t)S.queues.size(),
                      S.vs_tasks};
 }
 
-// The state built and uploaded (the pageable sources are read when this returns).
-void vs_build(Session& S) {
+void vs_spill_check(const Session& S, int32_t max_tasks, int rows) {
+    if (max_tasks <= kVictLds) return;
+    const size_t bytes = (size_t)rows * max_tasks * sizeof(VictRec);
+    if (bytes > (size_t)S.vs_spill_max)
+        throw Error(KBHIP_EUNSUPPORTED, "kbhip_heads_victims: the " + std::to_string(rows) +
+                                            " staging rows of one task for nodes of up to " +
+                                            std::to_string(max_tasks) + " tasks take " + std::to_string(bytes) +
+                                            " bytes, above victims_spill_max (" + std::to_string(S.vs_spill_max) +
+                                            " bytes)");
+}
+
+namespace {
+
+// The state built and uploaded (the pageable sources are read when this returns).  batch_rows > 0:
+// vs_spill_check before the upload.
+void vs_build(Session& S, int batch_rows) {
     const auto t0 = Clock::now();
     Session::VictHost H;
     vs_build_host(S, H);
@@ -109,6 +125,7 @@ void vs_build(Session& S) {
                                             " candidate tasks, " + std::to_string(H.job.size()) + " jobs and " +
                                             std::to_string(H.queue.size()) + " queues takes " +
                                             std::to_string(bytes >> 20) + " MB, above the 512 MB limit");
+    if (batch_rows > 0) vs_spill_check(S, H.max_tasks, batch_rows);
     // (every earlier call that read these buffers ended with a wait; a buffer that has to grow drains the stream)
     auto up = [&](DevBuf& b, const void* src, size_t n) {
         b.grow(S.stream, std::max<size_t>(n, 16), std::max<size_t>(n + n / 8, 4096));
@@ -183,6 +200,8 @@ int64_t vs_patch(Session& S) {
     return (int64_t)(nt + nj + nq);
 }
 
+}  // namespace
+
 // One call's constants: the task, the mode, and the victim functions of the mode's action (preempt for the
 // two preempt modes, reclaim for OTHER_QUEUES) tier by tier.
 VictHdr make_hdr(const Session& S, const HPod& p, int mode) {
@@ -205,9 +224,24 @@ VictHdr make_hdr(const Session& S, const HPod& p, int mode) {
     return h;
 }
 
+// Both tables made current (built, or the dirty records patched in one launch) and the pending count-table
+// changes flushed, for a call that opened the plugins.
+VictPrep vict_prepare(Session& S, int batch_rows) {
+    const bool vs_rebuilt = !S.vs_live;
+    if (!S.vict_live) vict_check_size(S);     // both tables' limits are checked before either is uploaded
+    if (vs_rebuilt) vs_build(S, batch_rows);  // (its own limit: after the host build, before the upload)
+    const bool rebuilt = vict_ensure(S);
+    int64_t launches = flush_tables(S);  // evictions / unevicts so far change pod-affinity predicates
+    const int64_t patched = vs_rebuilt ? 0 : vs_patch(S);
+    launches += patched ? 1 : 0;
+    return VictPrep{rebuilt, vs_rebuilt, patched, launches};
+}
+
+namespace {
+
 // What kbhip_head_victims and kbhip_walk_victims do before their own kernel: the plugins opened, the call's
-// header, both tables made current (built, or the dirty records patched in one launch) and the head sweep and
-// merge of kbhip_rank_victim_nodes enqueued — b_rank_head holds the head in stream order.
+// header, both tables made current and the head sweep and merge of kbhip_rank_victim_nodes enqueued —
+// b_rank_head holds the head in stream order.
 struct HeadPrep {
     VictHdr h;
     bool rebuilt, vs_rebuilt;
@@ -217,21 +251,37 @@ HeadPrep head_prepare(Session& S, const HPod& p, bool by_score, int mode) {
     Framework F(S);
     F.open_plugins();  // drf / proportion as OnSessionOpen leaves them (kbhip_apply_ops opens them the same way)
     const VictHdr h = make_hdr(S, p, mode);
-    const bool vs_rebuilt = !S.vs_live;
-    if (!S.vict_live) vict_check_size(S);  // both tables' limits are checked before either is uploaded
-    if (vs_rebuilt) vs_build(S);           // (its own limit: after the host build, before the upload)
-    const bool rebuilt = vict_ensure(S);
-    int64_t launches = flush_tables(S);  // evictions / unevicts so far change pod-affinity predicates
-    const int64_t patched = vs_rebuilt ? 0 : vs_patch(S);
-    launches += patched ? 1 : 0;
+    const VictPrep vp = vict_prepare(S, 0);
+    int64_t launches = vp.launches;
     vector<int32_t> own_node;
     vector<int64_t> own_sum;
     const VictArgs v = vict_args(S, p, mode, own_node, own_sum);
     launches += rank_head_enqueue(S, p.cls, by_score, &v);
-    return HeadPrep{h, rebuilt, vs_rebuilt, patched, launches};
+    return HeadPrep{h, vp.rebuilt, vp.vs_rebuilt, vp.patched, launches};
 }
 
 }  // namespace
+
+int64_t head_rows_unpack(const uint64_t* keys, const int32_t* rows, int cap, int stride, int dstride, bool by_score,
+                         int32_t* out_node, int32_t* out_score, int32_t* out_count, int32_t* out_evict,
+                         uint8_t* out_flags, int32_t* out_victim) {
+    const int64_t total = (int64_t)keys[kTopK];
+    int64_t max_count = 0;
+    for (int i = 0; i < cap; ++i) {
+        const bool in = i < total;
+        const int32_t* row = rows + (size_t)i * (3 + dstride);
+        out_node[i] = in ? key_idx(keys[i]) : -1;
+        if (out_score) out_score[i] = in && by_score ? key_score(keys[i]) : 0;
+        out_count[i] = row[0];
+        out_evict[i] = row[1];
+        out_flags[i] = (uint8_t)row[2];
+        int32_t* vrow = out_victim + (size_t)i * stride;
+        std::memcpy(vrow, row + 3, (size_t)dstride * sizeof(int32_t));
+        std::fill(vrow + dstride, vrow + stride, -1);
+        max_count = std::max<int64_t>(max_count, row[0]);
+    }
+    return max_count;
+}
 
 void vs_mark_dirty(Session& S, const int32_t* pod, int64_t n) {
     if (!S.vs_live) return;
@@ -282,20 +332,8 @@ int64_t head_victims_abi(Session& S, int pod, bool by_score, int mode, int cap, 
     const uint64_t* keys = S.h_vs_out.as<uint64_t>();
     const int32_t* rows = (const int32_t*)(S.h_vs_out.as<uint8_t>() + key_bytes);
     const int64_t total = (int64_t)keys[kTopK];
-    int64_t max_count = 0;
-    for (int i = 0; i < cap; ++i) {
-        const bool in = i < total;
-        const int32_t* row = rows + (size_t)i * (3 + dstride);
-        out_node[i] = in ? key_idx(keys[i]) : -1;
-        if (out_score) out_score[i] = in && by_score ? key_score(keys[i]) : 0;
-        out_count[i] = row[0];
-        out_evict[i] = row[1];
-        out_flags[i] = (uint8_t)row[2];
-        int32_t* vrow = out_victim + (size_t)i * stride;
-        std::memcpy(vrow, row + 3, (size_t)dstride * sizeof(int32_t));
-        std::fill(vrow + dstride, vrow + stride, -1);
-        max_count = std::max<int64_t>(max_count, row[0]);
-    }
+    const int64_t max_count = head_rows_unpack(keys, rows, cap, stride, dstride, by_score, out_node, out_score,
+                                               out_count, out_evict, out_flags, out_victim);
     if (out_info) {
         out_info[0] = rebuilt ? 1 : 0;
         out_info[1] = vs_rebuilt ? 1 : 0;

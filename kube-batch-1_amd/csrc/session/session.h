@@ -620,7 +620,7 @@ struct Session {
     // launch; more than vs_dirty_max pods waiting (option "victims_dirty_max") means a rebuild instead.
     // vs_pos[pod] = the pod's place in the CSR (-1: none); vs_tasks / vs_max_tasks: its length and its
     // longest node; vs_bytes: what the last build uploaded.  b_vs_spill: staging rows for nodes of more than
-    // kVictLds tasks; h_vs_patch / b_vs_patch: one call's patch lists; b_vs_out / h_vs_out: one call's head
+    // kVictLds tasks (kTopK of them, more for a kbhip_heads_victims batch); h_vs_patch / b_vs_patch: one call's patch lists; b_vs_out / h_vs_out: one call's head
     // keys and rows.
     bool vs_live = false;
     vector<int32_t> vs_pos, vs_dirty_pod, vs_dirty_job, vs_dirty_queue;
@@ -633,6 +633,9 @@ struct Session {
     // kbhip_walk_victims: option "walk_overlay_max" (tests; 0 = the full overlay): the touched jobs and the
     // touched queues a walk carries at most
     int32_t walk_ov_max = 0;
+    // kbhip_heads_victims: option "victims_spill_max" (bytes; tests lower it): the most b_vs_spill holds for
+    // one victims launch of a batch — a batch that needs more runs as consecutive request ranges
+    int64_t vs_spill_max = (int64_t)256 << 20;
     // kbhip_rank_heads (13_heads.cpp).  h_heads_in / b_heads_in: one call's upload — a PopCtrl image
     // of the call's own (slot i: request i's class, inter-pod min / max zero), its HeadDescs, the own-job
     // lists of its jobs; b_heads: the kernels' scratch (rank_heads_words); h_heads_out: kMaxChunk
@@ -1263,6 +1266,31 @@ int64_t vict_count_host(const Session& S, int mode, int q, const vector<int32_t>
 int64_t rank_heads_abi(Session& S, const int32_t* task_ids, int n_tasks, bool by_score, int mode, int cap,
                        int64_t* out_total, int32_t* out_node, int32_t* out_score, int32_t* out_cands,
                        int64_t* out_info);
+// The batch staging of kbhip_rank_heads, shared with kbhip_heads_victims (13_heads.cpp).  heads_stage fills
+// h_heads_in (the PopCtrl image, the HeadDescs, the own-job lists — one per distinct job of the batch, off in
+// list entries, job_of[i] = request i's entry of owns — and extra_bytes of the caller's behind them, at
+// h_extra / d_extra) once the candidate table is current; heads_enqueue uploads it in one copy and enqueues
+// the inter-pod prepasses (one per distinct class with priority terms: ipa_slots), the sweep and the merge,
+// after which b_heads holds request r's keys and count at word r (kTopK + 1).
+struct HeadsBatch {
+    struct Own {
+        int jb;
+        size_t off;
+        vector<int32_t> node;
+        vector<int64_t> sum;
+    };
+    vector<Own> owns;
+    int job_of[kMaxChunk];
+    int ipa_slots[kMaxChunk], n_ipa = 0;
+    int n = 0, mode = 0;
+    bool by_score = false;
+    size_t off_desc = 0, in_bytes = 0;
+    uint8_t* h_extra = nullptr;
+    uint8_t* d_extra = nullptr;
+};
+void heads_stage(Session& S, const int32_t* task_ids, int n, bool by_score, int mode, size_t extra_bytes,
+                 HeadsBatch& B);
+int heads_enqueue(Session& S, const HeadsBatch& B, int* bx);  // the launches made
 int64_t apply_ops(Session& S, const uint8_t* op, const int32_t* pod, const int32_t* node, int64_t n,
                   int64_t* out_launches);
 int64_t explain_tasks_abi(Session& S, const int32_t* task_ids, int n_tasks, uint8_t* out_verdict, int64_t* out_hist,
@@ -1274,6 +1302,30 @@ int64_t head_victims_abi(Session& S, int pod, bool by_score, int mode, int cap, 
                          int32_t* out_score, int32_t* out_count, int32_t* out_evict, uint8_t* out_flags,
                          int32_t* out_victim, int64_t* out_info);
 void vs_mark_dirty(Session& S, const int32_t* pod, int64_t n);
+// What kbhip_head_victims, kbhip_walk_victims and kbhip_heads_victims (16_heads_victims.cpp) share.
+// make_hdr: one request's constants (KBHIP_EUNSUPPORTED above kVictMaxCodes).  vict_prepare, with the
+// plugins open: both tables made current — built, or the dirty records patched in one launch — and the
+// pending count-table changes flushed; batch_rows > 0 (a batched call of that many rows per request):
+// vs_spill_check on a state built here, before anything of it is uploaded.  vs_spill_check: refuses
+// (KBHIP_EUNSUPPORTED) where `rows` spill rows of a state whose longest node has max_tasks tasks exceed
+// option "victims_spill_max".  vs_device_view: the device state.  head_rows_unpack: one request's keys and
+// device rows (3 + dstride words each) written to the ABI's arrays of cap entries (victim rows of stride,
+// the tail beyond dstride -1); returns the largest count.
+struct VictPrep {
+    bool rebuilt, vs_rebuilt;
+    int64_t patched, launches;
+};
+VictHdr make_hdr(const Session& S, const HPod& p, int mode);
+VictPrep vict_prepare(Session& S, int batch_rows);
+void vs_spill_check(const Session& S, int32_t max_tasks, int rows);
+VictState vs_device_view(const Session& S);
+int64_t head_rows_unpack(const uint64_t* keys, const int32_t* rows, int cap, int stride, int dstride, bool by_score,
+                         int32_t* out_node, int32_t* out_score, int32_t* out_count, int32_t* out_evict,
+                         uint8_t* out_flags, int32_t* out_victim);
+int64_t heads_victims_abi(Session& S, const int32_t* task_ids, int n_tasks, bool by_score, int mode, int cap,
+                          int stride, int64_t* out_total, int32_t* out_node, int32_t* out_score, int32_t* out_count,
+                          int32_t* out_evict, uint8_t* out_flags, int32_t* out_victim, int32_t* out_first,
+                          int64_t* out_info);
 void debug_victims(Session& S, int pod, int mode, int node, int stride, int32_t* out_count, int32_t* out_evict,
                    uint8_t* out_flags, int32_t* out_victim);
 bool debug_victim_table(Session& S, const string& name, vector<uint8_t>& out);

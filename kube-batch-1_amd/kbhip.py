@@ -23,6 +23,7 @@ STOP_ALL, STOP_UNASSIGNED, STOP_READY = 0, 1, 2
 OP_EVICT, OP_PIPELINE, OP_UNPIPELINE, OP_UNEVICT = 1, 2, 3, 4  # kbhip_apply_ops
 VICTIMS_OTHER_QUEUES, VICTIMS_QUEUE_OTHER_JOBS, VICTIMS_SAME_JOB = 1, 2, 3  # kbhip_rank_victim_nodes
 RANK_HEADS_MAX = 64  # KBHIP_RANK_HEADS_MAX: tasks per kbhip_rank_heads
+HEADS_VICTIMS_MAX = 64  # KBHIP_HEADS_VICTIMS_MAX: tasks per kbhip_heads_victims
 HEAD_VICTIMS_VALID, HEAD_VICTIMS_COVERS = 1, 2  # kbhip_head_victims: out_flags bits
 WALK_ASSIGNED, WALK_EXHAUSTED, WALK_HEAD_END, WALK_CAPACITY = 1, 2, 3, 4  # kbhip_walk_victims: stop reasons
 _WALK_INFO = ("stop", "total", "visited", "acted", "last_node", "last_score", "launches")
@@ -51,7 +52,7 @@ EXPORTS = ("kbhip_device_count", "kbhip_session_open", "kbhip_session_open_file"
            "kbhip_session_carry_snapshot", "kbhip_walk_visits", "kbhip_fit_deltas", "kbhip_rank_nodes",
            "kbhip_apply_ops", "kbhip_rank_victim_nodes", "kbhip_rank_heads", "kbhip_explain_tasks",
            "kbhip_debug_explain", "kbhip_head_victims", "kbhip_debug_victims", "kbhip_walk_victims",
-           "kbhip_debug_walk_victims")
+           "kbhip_debug_walk_victims", "kbhip_heads_victims")
 
 RED_MAX_U64, RED_MIN_I64, RED_MAX_I64, RED_SUM_I64 = 0, 1, 2, 3
 ALLREDUCE_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint64), ctypes.c_int32,
@@ -163,6 +164,8 @@ def lib() -> ctypes.CDLL:
         L.kbhip_head_victims.argtypes = [vp, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp]
         L.kbhip_head_victims.restype = i64
         L.kbhip_debug_victims.argtypes = [vp, i32, i32, i32, i32, vp, vp, vp, vp]
+        L.kbhip_heads_victims.argtypes = [vp, vp, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+        L.kbhip_heads_victims.restype = i64
         L.kbhip_walk_victims.argtypes = [vp, i32, i32, i32, i32, i32, i32, vp, vp, vp, i64, vp]
         L.kbhip_walk_victims.restype = i64
         L.kbhip_debug_walk_victims.argtypes = [vp, i32, i32, vp, i32, i64, vp, vp, vp, vp]
@@ -359,6 +362,41 @@ class Session:
         return (n, node[:cap], score[:cap], count[:cap], evict[:cap], flags[:cap],
                 victim[: cap * stride].reshape(cap, stride),
                 dict(zip(("rebuilt", "state_rebuilt", "patched", "launches", "max_count"), map(int, info))))
+
+    def heads_victims(self, task_ids, by_score: bool = True, victims: int = VICTIMS_OTHER_QUEUES,
+                      cap: int = 64, stride: int = 16):
+        """kbhip_heads_victims: head_victims for up to HEADS_VICTIMS_MAX pending
+        tasks of the session as it stands in one call: (totals[n], nodes[n,
+        cap], scores[n, cap], counts[n, cap], evicts[n, cap], flags[n, cap],
+        victim_rows[n, cap, stride], first[n], info).  Row i is what
+        head_victims(task_ids[i], by_score, victims, cap, stride) answers, no
+        eviction carried between tasks; first[i] is the index of task i's first
+        head entry with HEAD_VICTIMS_VALID, or -1.
+        info: {"rebuilt", "state_rebuilt", "patched", "launches", "max_count",
+        "victim_launches"}."""
+        ids = np.ascontiguousarray(task_ids, dtype=np.int32).reshape(-1)
+        n, cap, stride = int(ids.size), int(cap), int(stride)
+        rows = max(n, 1) * max(cap, 1)
+        total = np.zeros(max(n, 1), np.int64)
+        node = np.full(rows, -1, np.int32)
+        score = np.zeros(rows, np.int32)
+        count = np.zeros(rows, np.int32)
+        evict = np.zeros(rows, np.int32)
+        flags = np.zeros(rows, np.uint8)
+        victim = np.full(rows * max(stride, 1), -1, np.int32)
+        first = np.full(max(n, 1), -1, np.int32)
+        info = np.zeros(6, np.int64)
+        r = int(lib().kbhip_heads_victims(self._h, _p(ids), n, int(by_score), int(victims), cap, stride, _p(total),
+                                          _p(node), _p(score), _p(count), _p(evict), _p(flags), _p(victim),
+                                          _p(first), _p(info)))
+        _check(r if r < 0 else 0)
+        k = n * cap
+        shape = (n, cap)
+        return (total[:n].copy(), node[:k].reshape(shape), score[:k].reshape(shape), count[:k].reshape(shape),
+                evict[:k].reshape(shape), flags[:k].reshape(shape), victim[: k * stride].reshape(n, cap, stride),
+                first[:n].copy(),
+                dict(zip(("rebuilt", "state_rebuilt", "patched", "launches", "max_count", "victim_launches"),
+                         map(int, info))))
 
     def walk_victims(self, task_id: int, by_score: bool = True, victims: int = VICTIMS_OTHER_QUEUES,
                      cap: int = 64, after=None, cap_ops: int = 4096):
