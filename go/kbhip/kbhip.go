@@ -548,6 +548,48 @@ func (e *Engine) WalkVictims(task int32, byScore bool, victims int32, cap int, a
 	return ops[:n], pods[:n], nodes[:n], info, nil
 }
 
+// WalkVictimsFromInfo says how a WalkVictimsFrom call ended and what it did
+// (out_info of kbhip_walk_victims_from).
+type WalkVictimsFromInfo struct {
+	Stop         int   // a Walk* reason: WalkExhausted = every node behind the resume point was decided, WalkHeadEnd = the window is used up and nodes remain
+	Remaining    int64 // entries of the pruned walk behind the resume point at the call
+	Visited      int64 // window entries decided
+	Acted        int64 // nodes evicted from
+	ResumeNode   int32 // the resume point: the last entry passed over or acted on (the call's own afterNode if none)
+	ResumeScore  int32 // its score (0 with byScore false)
+	Launches     int64
+	Rebuilt      bool  // the candidate table was built by this call
+	StateRebuilt bool  // the victim state was built by this call
+	Patched      int64 // records of earlier ApplyOps batches patched into it
+	LastNode     int32 // the last acted-on node, -1 if none
+	FirstValid   int32 // window index of the first entry VALID against the session as it stands, -1 if none
+}
+
+// WalkVictimsFrom runs one window (up to 64 entries) of a task's eviction walk
+// behind a resume point (kbhip_walk_victims_from).  ops / pods / nodes go to
+// ApplyOps unchanged.  afterNode < 0 starts at the top; after a WalkHeadEnd or
+// WalkCapacity stop apply the ops and call again with ResumeNode /
+// ResumeScore: the loop reaches WalkAssigned or WalkExhausted for a walk of
+// any length.  1 <= cap <= 64, capOps >= 1.
+func (e *Engine) WalkVictimsFrom(task int32, byScore bool, victims int32, cap int, afterNode, afterScore int32, capOps int) (ops []uint8, pods, nodes []int32, info WalkVictimsFromInfo, err error) {
+	if cap < 1 || cap > 64 || capOps < 1 { // (also keeps &x[0] below off empty slices)
+		return nil, nil, nil, info, fmt.Errorf("kbhip walk_victims_from: cap %d (1..64), capOps %d (>= 1)", cap, capOps)
+	}
+	ops, pods, nodes = make([]uint8, capOps), make([]int32, capOps), make([]int32, capOps)
+	var raw [10]C.int64_t
+	n := C.kbhip_walk_victims_from(e.s, C.int32_t(task), boolI32(byScore), C.int32_t(victims), C.int32_t(cap),
+		C.int32_t(afterNode), C.int32_t(afterScore), (*C.uint8_t)(unsafe.Pointer(&ops[0])),
+		(*C.int32_t)(unsafe.Pointer(&pods[0])), (*C.int32_t)(unsafe.Pointer(&nodes[0])), C.int64_t(capOps), &raw[0])
+	if n < 0 {
+		return nil, nil, nil, info, lastErr("walk_victims_from", C.int(n))
+	}
+	info = WalkVictimsFromInfo{Stop: int(raw[0]), Remaining: int64(raw[1]), Visited: int64(raw[2]),
+		Acted: int64(raw[3]), ResumeNode: int32(raw[4]), ResumeScore: int32(raw[5]), Launches: int64(raw[6]),
+		Rebuilt: raw[7]&1 != 0, StateRebuilt: raw[7]&2 != 0, Patched: int64(raw[7]) >> 8, LastNode: int32(raw[8]),
+		FirstValid: int32(raw[9])}
+	return ops[:n], pods[:n], nodes[:n], info, nil
+}
+
 // The verdict codes of ExplainTasks (KBHIP_WHY_*): the low four bits of a
 // verdict byte; the WhyShort* bits accompany the codes 0..2.
 const (

@@ -530,8 +530,7 @@ int64_t kbhip_heads_victims(kb_session* s, const int32_t* task_ids, int32_t n_ta
  * the loop has left behind.  A host resumes after KBHIP_WALK_CAPACITY (apply the
  * ops, call again after out_info[4] / out_info[5]) and after
  * KBHIP_WALK_HEAD_END while the resume point is inside the new 64-entry head;
- * past the head it falls back to kbhip_rank_victim_nodes windows and its own
- * victim functions.
+ * past the head kbhip_walk_victims_from (below) goes on.
  * A step is all or nothing: when a valid node's prefix plus one slot for a
  * possible pipeline does not fit what is left of cap_ops, or a node the walk
  * would go on from touches more distinct jobs or queues than the carried state
@@ -565,6 +564,64 @@ int64_t kbhip_walk_victims(kb_session* s, int32_t task_id, int32_t by_score, int
                            int32_t after_node /* -1: from the top */, int32_t after_score,
                            uint8_t* out_op, int32_t* out_pod, int32_t* out_node, int64_t cap_ops,
                            int64_t* out_info /* optional, 8 */);
+
+/* kbhip_walk_victims_from <- the same node loop over a walk of any length, one
+ * window of up to 64 entries per call.
+ * The window is the first up to 64 entries of the task's pruned walk
+ * (kbhip_rank_victim_nodes' order and test, on the session as it stands) among
+ * the nodes whose key is below the resume key: the key the head sweep forms for
+ * (after_score, after_node), the score ignored with by_score 0, where the
+ * sweep's keys carry none.  Nodes at or above the resume key take no window
+ * slot and are not counted.  after_node -1: no bound — the window is
+ * kbhip_walk_victims' head.
+ * The window's first min(cap, 64) entries are decided in order with
+ * kbhip_walk_victims' semantics, unchanged: an entry that is not VALID is passed
+ * over, a VALID node's prefix is evicted, a COVERS node also pipelines the task
+ * and stops the walk with KBHIP_WALK_ASSIGNED, otherwise the evictions are
+ * carried to the entries after it.  cap_ops, the all-or-nothing steps, the
+ * carried state's capacities (option "walk_overlay_max"), "the first node a call
+ * acts on is taken" and the op format for kbhip_apply_ops are kbhip_walk_victims'.
+ * Stop reasons: KBHIP_WALK_ASSIGNED and KBHIP_WALK_CAPACITY as there;
+ *   KBHIP_WALK_EXHAUSTED  every node behind the resume point was decided.
+ *   KBHIP_WALK_HEAD_END   `cap` or 64 window entries are used up and nodes
+ *     remain behind them: apply the ops (if any) and call again from
+ *     out_info[4] / out_info[5].
+ * The resume point a call returns is the last window entry it passed over or
+ * acted on; a node before which the walk stopped with KBHIP_WALK_CAPACITY is not
+ * behind it, so the next call meets that node again.  When no entry was passed
+ * over or acted on it is the call's own after_node / after_score.
+ * Host protocol: call, send the ops through kbhip_apply_ops, and after
+ * KBHIP_WALK_HEAD_END or KBHIP_WALK_CAPACITY call again from out_info[4] /
+ * out_info[5]; the loop reaches KBHIP_WALK_ASSIGNED or KBHIP_WALK_EXHAUSTED for
+ * a walk of any length, and the concatenated ops are the reference's for that
+ * task: one ranking and one node loop.  Within a window the walk order is
+ * fixed before the first eviction, as in kbhip_walk_victims.  One limit:
+ * between two windows the host has applied evictions, and the next window is
+ * ranked on the session as it then stands, where the reference ranks once
+ * per task.  That is the
+ * rank-once order wherever kbhip_walk_victims' own resume is — no ranking reads
+ * Releasing, and the victim test of the nodes behind the resume point is
+ * untouched — except for task classes whose predicates read pod-affinity
+ * targets that an applied eviction removed: for those a node behind the resume
+ * point can enter or leave the later windows.
+ * out_info (optional, 10 entries): [0] the stop reason, [1] the entries of the
+ * pruned walk behind the resume point at the call (the bounded sweep's passing
+ * count), [2] entries decided (counted as kbhip_walk_victims counts them: a
+ * node refused with KBHIP_WALK_CAPACITY included), [3] nodes acted on, [4] the
+ * resume point's node (-1: from the top), [5] its score (0 with by_score 0),
+ * [6] kernel launches (kbhip_walk_victims' and one: the pre-pass that decides
+ * the window's entries side by side), [7] as kbhip_walk_victims' [7], [8] the
+ * last acted-on node (-1: none), [9] the window index of the first entry whose
+ * decision against the session as it stands is VALID (-1: none: the walk
+ * passes over all of them without its serial loop).
+ * Read-only as kbhip_walk_victims.  The whole call is validated before any
+ * device work, and a refused call writes nothing.  KBHIP_EINVAL and
+ * KBHIP_EUNSUPPORTED: as kbhip_walk_victims. */
+int64_t kbhip_walk_victims_from(kb_session* s, int32_t task_id, int32_t by_score, int32_t victims /* KBHIP_VICTIMS_* */,
+                                int32_t cap /* 1..64 window entries to decide */,
+                                int32_t after_node /* -1: from the top */, int32_t after_score,
+                                uint8_t* out_op, int32_t* out_pod, int32_t* out_node, int64_t cap_ops,
+                                int64_t* out_info /* optional, 10 */);
 
 /* kbhip_explain_tasks <- why each node is, or is not, a node of the allocate
  * walk of up to KBHIP_EXPLAIN_MAX pending tasks, on the session as it stands:

@@ -94,11 +94,15 @@ __device__ __forceinline__ bool vict_keep(const VictArgs& v, const Vict4& a) {
 // request's inter-pod min / max; stride: the nodes one step of the grid
 // covers (gridDim.x * kBlock).  s_top / s_cnt: the block's LDS (the caller's,
 // so that a kernel with two instantiations of the body declares it once).
-template <bool PLAIN, bool FILT>
+// BOUND (kbhip_walk_victims_from): a key at or above `bound` — a node the
+// caller's loop has left behind — becomes 0 before the count and the top-64
+// test, so the count is the count below the bound and such a node enters no
+// list; without BOUND bound is never read.
+template <bool PLAIN, bool FILT, bool BOUND = false>
 __device__ __forceinline__ void rank_head(const Conf& cf, const NodeCols& nc, const DevTables& t, const TaskClass& c,
                                           const PopCtrl* ctrl, int by_score, int slot, int stride, uint64_t* lists,
                                           uint32_t* bcnt, const VictArgs& v, uint64_t (*s_top)[64],
-                                          uint32_t* s_cnt) {
+                                          uint32_t* s_cnt, uint64_t bound = 0) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     uint64_t top = 0;  // lane i: the wave's i-th best key so far
     uint32_t cnt = 0;  // passing nodes of the wave (uniform)
@@ -146,6 +150,9 @@ __device__ __forceinline__ void rank_head(const Conf& cf, const NodeCols& nc, co
         if constexpr (FILT) {
             if (!vict_keep(v, va)) k = 0;  // (lanes past the last node: va is zero, k already is)
         }
+        if constexpr (BOUND) {
+            if (k >= bound) k = 0;
+        }
         cnt += (uint32_t)__popcll(__ballot(k != 0));
         if (__ballot(k > readlane64(top, 63)) == 0) continue;  // uniform: nothing enters the top 64
         top = wave_merge_desc(top, wave_sort_desc(k));
@@ -176,6 +183,16 @@ __global__ __launch_bounds__(kBlock) void k_rank_head_vict(Conf cf, NodeCols nc,
     __shared__ uint64_t s_top[kHeadWaves][64];
     __shared__ uint32_t s_cnt[kHeadWaves];
     rank_head<PLAIN, true>(cf, nc, t, c, ctrl, by_score, 0, gridDim.x * kBlock, lists, bcnt, v, s_top, s_cnt);
+}
+// kbhip_walk_victims_from's sweep: k_rank_head_vict over the nodes whose key is below `bound` (> 0)
+template <bool PLAIN>
+__global__ __launch_bounds__(kBlock) void k_rank_head_vict_from(Conf cf, NodeCols nc, DevTables t, TaskClass c,
+                                                                const PopCtrl* ctrl, int by_score, uint64_t* lists,
+                                                                uint32_t* bcnt, VictArgs v, uint64_t bound) {
+    __shared__ uint64_t s_top[kHeadWaves][64];
+    __shared__ uint32_t s_cnt[kHeadWaves];
+    rank_head<PLAIN, true, true>(cf, nc, t, c, ctrl, by_score, 0, gridDim.x * kBlock, lists, bcnt, v, s_top, s_cnt,
+                                 bound);
 }
 
 __device__ __forceinline__ void rank_head_merge(const uint64_t* lists, const uint32_t* bcnt, int nblk,
@@ -281,14 +298,22 @@ int rank_head_blocks(int n_nodes) {
 size_t rank_head_words() { return (size_t)(kTopK + 1) + (size_t)kHeadMaxBlocks * 64 + kHeadMaxBlocks / 2; }
 
 hipError_t launch_rank_head(const Conf& cf, const NodeCols& nc, const DevTables& t, const TaskClass& c,
-                            const PopCtrl* ctrl, int by_score, const VictArgs* v, uint64_t* scratch, hipStream_t st) {
+                            const PopCtrl* ctrl, int by_score, const VictArgs* v, uint64_t* scratch, hipStream_t st,
+                            uint64_t bound) {
     static_assert(kTopK == 64, "one key per lane");
     uint64_t* out = scratch;
     uint64_t* lists = scratch + kTopK + 1;
     uint32_t* bcnt = reinterpret_cast<uint32_t*>(lists + (size_t)kHeadMaxBlocks * 64);
     const int grid = rank_head_blocks(nc.n);
     const bool plain = by_score && !c.aff && c.ipa_n == 0;
-    if (v && plain)
+    if (bound != 0 && !v) return hipErrorInvalidValue;  // (the bounded sweep exists for the pruned walk only)
+    if (bound != 0 && plain)
+        hipLaunchKernelGGL((k_rank_head_vict_from<true>), dim3(grid), dim3(kBlock), 0, st, cf, nc, t, c, ctrl,
+                           by_score, lists, bcnt, *v, bound);
+    else if (bound != 0)
+        hipLaunchKernelGGL((k_rank_head_vict_from<false>), dim3(grid), dim3(kBlock), 0, st, cf, nc, t, c, ctrl,
+                           by_score, lists, bcnt, *v, bound);
+    else if (v && plain)
         hipLaunchKernelGGL((k_rank_head_vict<true>), dim3(grid), dim3(kBlock), 0, st, cf, nc, t, c, ctrl, by_score,
                            lists, bcnt, *v);
     else if (v)

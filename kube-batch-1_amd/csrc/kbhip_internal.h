@@ -122,9 +122,11 @@ struct VictArgs {
     int64_t rc, rm, rg;
 };
 // The head's launch; v non-null (kbhip_rank_victim_nodes): the test above applied by the lane that
-// evaluates the node (the count is the kept nodes').
+// evaluates the node (the count is the kept nodes').  bound != 0 (kbhip_walk_victims_from, v non-null):
+// the sweep's bounded variant — only nodes whose key is below bound are counted or listed.
 hipError_t launch_rank_head(const Conf& cf, const NodeCols& nc, const DevTables& t, const TaskClass& c,
-                            const PopCtrl* ctrl, int by_score, const VictArgs* v, uint64_t* scratch, hipStream_t st);
+                            const PopCtrl* ctrl, int by_score, const VictArgs* v, uint64_t* scratch, hipStream_t st,
+                            uint64_t bound = 0);
 // kbhip_rank_heads: the heads of n_req (1 .. kMaxChunk) tasks of one session in
 // one sweep launch (grid (bx, n_req), blockIdx.y = the request) and one merge
 // launch (grid n_req).  Request r is d_desc[r] in device memory: its class,
@@ -319,6 +321,19 @@ hipError_t launch_walk_victims(const VictState& st, const VictHdr& h, const uint
                                int task, int node_base, VictRec* spill, int spill_stride, int ov_cap_j, int ov_cap_q,
                                int64_t cap_ops, int64_t* out_info, int32_t* out_pod, int32_t* out_node,
                                hipStream_t stm);
+// kbhip_walk_victims_from (kbhip_victims.hip): the walk over a window — `head` is the bounded sweep's
+// result, every entry of it behind the caller's resume point — in two launches.  k_walk_flags: the
+// window's first `cap` entries decided side by side against the state as it stands, one wave each
+// (head_victims_row with no victim row), flags[3 i ..] = entry i's count, evict, flags; lds_recs and spill
+// (cap rows) as launch_heads_victims.  k_walk_victims_from: one block; the entries before the first VALID
+// one are passed over by their flag (no eviction precedes them, so the flag is the walk's answer), from it
+// on k_walk_victims' loop.  out_info (10 int64): stop, total, visited, acted, the resume point's node and
+// score (-1, 0: no entry was passed over or acted on), ops, the resume point's window index (-1), the last
+// acted-on node (-1), the first VALID entry's window index (-1).
+hipError_t launch_walk_victims_from(const VictState& st, const VictHdr& h, const uint64_t* head, int cap, int task,
+                                    int node_base, int lds_recs, VictRec* spill, int spill_stride, int ov_cap_j,
+                                    int ov_cap_q, int64_t cap_ops, int32_t* flags, int64_t* out_info,
+                                    int32_t* out_pod, int32_t* out_node, hipStream_t stm);
 
 // Selection-key format of a batched launch: 32-bit keys when the class's
 // score range and the node count fit (kbhip_kernels.hip, PopArgs).

@@ -32,6 +32,10 @@
 //                    order, staging each node as above under an overlay of
 //                    the evictions of the entries before it (described at the
 //                    kernel).
+//   k_walk_flags, k_walk_victims_from
+//                    kbhip_walk_victims_from: the entries of a window behind
+//                    the caller's resume point decided side by side (flags
+//                    only), then the walk from the first entry that can act.
 //   k_victims_patch  the records kbhip_apply_ops left dirty, one thread each.
 // Stores are plain vector stores; nothing is atomic, no block waits for another.
 #include <hip/hip_runtime.h>
@@ -194,6 +198,107 @@ __global__ __launch_bounds__(kWalkBlock) void k_walk_victims(VictState st, VictH
         out_info[6] = s_c.n_ops;
         out_info[7] = 0;
     }
+}
+
+// kbhip_walk_victims_from, the stateless pre-pass: window entry blockIdx.x decided against the state as it
+// stands by one wave — head_victims_row with no victim row (stride 0: vict_decide stores no victim), so
+// flags[3 i ..] = entry i's count, evict, flags and nothing else is written.  Dynamic LDS as k_heads_victims.
+__global__ __launch_bounds__(64) void k_walk_flags(VictState st, VictHdr h, const uint64_t* __restrict__ head, int cap,
+                                                   int node_base, int lds_recs, VictRec* spill, int spill_stride,
+                                                   int32_t* flags) {
+    const int i = blockIdx.x;
+    if (i >= cap || i >= kTopK) return;
+    head_victims_row(st, h, head, i, 0, node_base, s_dyn_rec, lds_recs,
+                     spill ? spill + (size_t)i * spill_stride : nullptr, spill_stride, flags + 3 * i);
+}
+
+// kbhip_walk_victims_from, the walk: k_walk_victims over a window every entry of which is behind the
+// caller's resume point (the bounded sweep left the others out), so no entry is skipped by its key and an
+// entry's window index is the number of entries decided before it.  The entries before the first one the
+// pre-pass found VALID (a ballot over the flag words) are passed over without staging: no eviction
+// precedes them, so the overlay is empty and the stateless flag is the walk's answer.  From that entry on
+// the loop is k_walk_victims' — that entry too is decided by walk_step, and the entries after it never by
+// their flag: carried state can turn an invalid node valid.  s_res: the window index of the resume point,
+// the last entry passed over or acted on (an entry refused with kWalkCapacity is met again by the next call).
+__global__ __launch_bounds__(kWalkBlock) void k_walk_victims_from(VictState st, VictHdr h0, const uint64_t* head,
+                                                                  int cap, const int32_t* flags, int task,
+                                                                  int node_base, VictRec* spill, int spill_stride,
+                                                                  int ov_cap_j, int ov_cap_q, int64_t cap_ops,
+                                                                  int64_t* out_info, int32_t* out_pod,
+                                                                  int32_t* out_node) {
+    __shared__ VictRec s_rec[kVictLds];
+    __shared__ WalkOverlay s_ov;
+    __shared__ VictHdr s_h;
+    __shared__ WalkCtl s_c;
+    __shared__ int s_first, s_res;
+    const int tid = threadIdx.x;
+    const uint64_t total = head[kTopK];
+    const int in_win = total < (uint64_t)kTopK ? (int)total : kTopK;
+    const int lim = cap < in_win ? cap : in_win;  // the entries this call decides
+    if (tid < 64) {                               // (wave 0: one lane per window entry)
+        const uint64_t valid = __ballot(tid < lim && (flags[3 * tid + 2] & 1) != 0);
+        if (tid == 0) {
+            const int first = valid ? __ffsll((unsigned long long)valid) - 1 : -1;
+            const int passed = first < 0 ? lim : first;
+            s_first = first;
+            s_res = passed - 1;
+            s_h = h0;
+            walk_ov_init(s_ov, ov_cap_j, ov_cap_q);
+            s_c = WalkCtl{0, cap_ops, 0, passed, 0, -1, 0, task};
+        }
+    }
+    __syncthreads();
+    int i = s_first < 0 ? lim : s_first;
+    for (; i < lim; ++i) {  // (every condition below is uniform over the block)
+        const uint64_t key = head[i];
+        const int node = key_idx(key) - node_base;
+        int off = 0, n = 0;  // n == 0: nothing to stage (walk_step still counts the visit)
+        if (key != 0 && node >= 0 && node < st.n_nodes) {
+            off = st.node_off[node];
+            n = st.node_off[node + 1] - off;
+            if (off < 0 || n < 0 || off + n > st.n_tasks || (n > kVictLds && (!spill || n > spill_stride))) n = 0;
+        }
+        VictRec* const rec = n <= kVictLds ? s_rec : spill;
+        for (int k = tid; k < n; k += kWalkBlock) vict_stage_walk(st, s_h, s_ov, off + k, rec[k]);
+        __syncthreads();
+        for (int k = tid; k < n; k += kWalkBlock) vict_link(rec, k);
+        __syncthreads();
+        if (tid == 0) {
+            const int acted = s_c.acted;
+            walk_step(s_h, s_ov, s_c, rec, n, key_idx(key), key_score(key), out_pod, out_node);
+            if (s_c.stop != kWalkCapacity || s_c.acted != acted) s_res = i;  // passed over or acted on
+        }
+        __syncthreads();
+        if (s_c.stop != 0) break;
+    }
+    if (tid == 0) {
+        int stop = s_c.stop;
+        if (stop == 0) stop = (uint64_t)i < total ? kWalkHeadEnd : kWalkExhausted;
+        const int res = s_res;
+        out_info[0] = stop;
+        out_info[1] = (int64_t)total;
+        out_info[2] = s_c.visited;
+        out_info[3] = s_c.acted;
+        out_info[4] = res >= 0 ? key_idx(head[res]) : -1;
+        out_info[5] = res >= 0 ? key_score(head[res]) : 0;
+        out_info[6] = s_c.n_ops;
+        out_info[7] = res;
+        out_info[8] = s_c.last_node;
+        out_info[9] = s_first;
+    }
+}
+
+hipError_t launch_walk_victims_from(const VictState& st, const VictHdr& h, const uint64_t* head, int cap, int task,
+                                    int node_base, int lds_recs, VictRec* spill, int spill_stride, int ov_cap_j,
+                                    int ov_cap_q, int64_t cap_ops, int32_t* flags, int64_t* out_info,
+                                    int32_t* out_pod, int32_t* out_node, hipStream_t stm) {
+    if (cap < 1 || cap > kTopK || cap_ops < 1 || lds_recs < 1 || lds_recs > kVictLds) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_walk_flags, dim3(cap), dim3(64), (size_t)lds_recs * sizeof(VictRec), stm, st, h, head, cap,
+                       node_base, lds_recs, spill, spill_stride, flags);
+    hipLaunchKernelGGL(k_walk_victims_from, dim3(1), dim3(kWalkBlock), 0, stm, st, h, head, cap,
+                       (const int32_t*)flags, task, node_base, spill, spill_stride, ov_cap_j, ov_cap_q, cap_ops,
+                       out_info, out_pod, out_node);
+    return hipGetLastError();
 }
 
 hipError_t launch_walk_victims(const VictState& st, const VictHdr& h, const uint64_t* head, int cap, uint64_t after_key,

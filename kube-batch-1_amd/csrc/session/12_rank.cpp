@@ -139,8 +139,8 @@ VictArgs vict_args(Session& S, const HPod& p, int mode, vector<int32_t>& own_nod
 }
 
 // The head of the walk of class cls, enqueued: afterwards (in stream order) b_rank_head holds the kTopK
-// best keys and the count.  Nothing is copied back or waited for.
-int rank_head_enqueue(Session& S, int cls, bool by_score, const VictArgs* v) {
+// best keys and the count.  Nothing is copied back or waited for.  bound != 0 (with v): the bounded sweep.
+int rank_head_enqueue(Session& S, int cls, bool by_score, const VictArgs* v, uint64_t bound) {
     const TaskClass& c = S.classes[cls];
     int launches = 0;
     if (!S.b_rank_head.p) S.b_rank_head.alloc<uint64_t>(rank_head_words());
@@ -151,7 +151,7 @@ int rank_head_enqueue(Session& S, int cls, bool by_score, const VictArgs* v) {
         launches += 1;
     }
     HIPCHK(launch_rank_head(S.conf, S.nc, S.tab, c, S.d_ctrl, by_score ? 1 : 0, v, (uint64_t*)S.b_rank_head.p,
-                            S.stream));
+                            S.stream, bound));
     return launches + 2;  // sweep + merge
 }
 

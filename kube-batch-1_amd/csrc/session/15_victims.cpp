@@ -237,17 +237,11 @@ VictPrep vict_prepare(Session& S, int batch_rows) {
     return VictPrep{rebuilt, vs_rebuilt, patched, launches};
 }
 
-namespace {
-
-// What kbhip_head_victims and kbhip_walk_victims do before their own kernel: the plugins opened, the call's
-// header, both tables made current and the head sweep and merge of kbhip_rank_victim_nodes enqueued —
-// b_rank_head holds the head in stream order.
-struct HeadPrep {
-    VictHdr h;
-    bool rebuilt, vs_rebuilt;
-    int64_t patched, launches;
-};
-HeadPrep head_prepare(Session& S, const HPod& p, bool by_score, int mode) {
+// What kbhip_head_victims, kbhip_walk_victims and kbhip_walk_victims_from do before their own kernel: the
+// plugins opened, the call's header, both tables made current and the head sweep and merge of
+// kbhip_rank_victim_nodes enqueued — b_rank_head holds the head in stream order (bound != 0: the head
+// among the nodes whose key is below it).
+HeadPrep head_prepare(Session& S, const HPod& p, bool by_score, int mode, uint64_t bound) {
     Framework F(S);
     F.open_plugins();  // drf / proportion as OnSessionOpen leaves them (kbhip_apply_ops opens them the same way)
     const VictHdr h = make_hdr(S, p, mode);
@@ -256,11 +250,9 @@ HeadPrep head_prepare(Session& S, const HPod& p, bool by_score, int mode) {
     vector<int32_t> own_node;
     vector<int64_t> own_sum;
     const VictArgs v = vict_args(S, p, mode, own_node, own_sum);
-    launches += rank_head_enqueue(S, p.cls, by_score, &v);
+    launches += rank_head_enqueue(S, p.cls, by_score, &v, bound);
     return HeadPrep{h, vp.rebuilt, vp.vs_rebuilt, vp.patched, launches};
 }
-
-}  // namespace
 
 int64_t head_rows_unpack(const uint64_t* keys, const int32_t* rows, int cap, int stride, int dstride, bool by_score,
                          int32_t* out_node, int32_t* out_score, int32_t* out_count, int32_t* out_evict,

@@ -1338,9 +1338,23 @@ int64_t debug_walk_victims(Session& S, int pod, int mode, const int32_t* nodes, 
 // The head path of rank_victim_nodes_abi, shared with kbhip_head_victims.  vict_args: the job's own list
 // uploaded and the call's VictArgs.  rank_head_enqueue: the control block, the inter-pod prepass where the
 // class has one, the sweep and the merge on the session's stream (b_rank_head holds the result once they
-// ran); returns the launches it made.
+// ran); returns the launches it made.  bound != 0 (v non-null): the sweep's bounded variant, the head among
+// the nodes whose key is below bound.
 VictArgs vict_args(Session& S, const HPod& p, int mode, vector<int32_t>& own_node, vector<int64_t>& own_sum);
-int rank_head_enqueue(Session& S, int cls, bool by_score, const VictArgs* v);
+int rank_head_enqueue(Session& S, int cls, bool by_score, const VictArgs* v, uint64_t bound = 0);
+// What kbhip_head_victims, kbhip_walk_victims (15_victims.cpp) and kbhip_walk_victims_from
+// (17_walk_from.cpp) do before their own kernel: the plugins opened, the call's header, vict_prepare and
+// rank_head_enqueue in a victim mode.
+struct HeadPrep {
+    VictHdr h;
+    bool rebuilt, vs_rebuilt;
+    int64_t patched, launches;
+};
+HeadPrep head_prepare(Session& S, const HPod& p, bool by_score, int mode, uint64_t bound = 0);
+// kbhip_walk_victims_from (17_walk_from.cpp): one window of a task's eviction walk behind a resume point
+int64_t walk_victims_from_abi(Session& S, int pod, bool by_score, int mode, int cap, int after_node, int after_score,
+                              uint8_t* out_op, int32_t* out_pod, int32_t* out_node, int64_t cap_ops,
+                              int64_t* out_info);
 
 }  // namespace kbhip
 

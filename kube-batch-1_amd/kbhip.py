@@ -33,6 +33,16 @@ def _walk_info(info):
     d = dict(zip(_WALK_INFO, map(int, info[:7])))
     d.update(rebuilt=int(info[7]) & 1, state_rebuilt=(int(info[7]) >> 1) & 1, patched=int(info[7]) >> 8)
     return d
+
+
+_WALK_FROM_INFO = ("stop", "remaining", "visited", "acted", "resume_node", "resume_score", "launches")
+
+
+def _walk_from_info(info):
+    d = dict(zip(_WALK_FROM_INFO, map(int, info[:7])))
+    d.update(rebuilt=int(info[7]) & 1, state_rebuilt=(int(info[7]) >> 1) & 1, patched=int(info[7]) >> 8,
+             last_node=int(info[8]), first_valid=int(info[9]))
+    return d
 # kbhip_explain_tasks: the verdict codes (low four bits of a verdict byte), the short bits of codes 0..2
 (WHY_FITS_IDLE, WHY_FITS_RELEASING, WHY_RESOURCES, WHY_POD_COUNT, WHY_NODE_SELECTOR, WHY_HOST_PORTS,
  WHY_UNSCHEDULABLE, WHY_TAINTS, WHY_POD_AFFINITY, WHY_SCORE_ERROR) = range(10)
@@ -52,7 +62,7 @@ EXPORTS = ("kbhip_device_count", "kbhip_session_open", "kbhip_session_open_file"
            "kbhip_session_carry_snapshot", "kbhip_walk_visits", "kbhip_fit_deltas", "kbhip_rank_nodes",
            "kbhip_apply_ops", "kbhip_rank_victim_nodes", "kbhip_rank_heads", "kbhip_explain_tasks",
            "kbhip_debug_explain", "kbhip_head_victims", "kbhip_debug_victims", "kbhip_walk_victims",
-           "kbhip_debug_walk_victims", "kbhip_heads_victims")
+           "kbhip_debug_walk_victims", "kbhip_heads_victims", "kbhip_walk_victims_from")
 
 RED_MAX_U64, RED_MIN_I64, RED_MAX_I64, RED_SUM_I64 = 0, 1, 2, 3
 ALLREDUCE_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint64), ctypes.c_int32,
@@ -170,6 +180,8 @@ def lib() -> ctypes.CDLL:
         L.kbhip_walk_victims.restype = i64
         L.kbhip_debug_walk_victims.argtypes = [vp, i32, i32, vp, i32, i64, vp, vp, vp, vp]
         L.kbhip_debug_walk_victims.restype = i64
+        L.kbhip_walk_victims_from.argtypes = [vp, i32, i32, i32, i32, i32, i32, vp, vp, vp, i64, vp]
+        L.kbhip_walk_victims_from.restype = i64
         _lib = L
     return _lib
 
@@ -416,6 +428,27 @@ class Session:
                                          _p(op), _p(pod), _p(node), cap_ops, _p(info)))
         _check(n if n < 0 else 0)
         return op[:n].copy(), pod[:n].copy(), node[:n].copy(), _walk_info(info)
+
+    def walk_victims_from(self, task_id: int, by_score: bool = True, victims: int = VICTIMS_OTHER_QUEUES,
+                          cap: int = 64, after=None, cap_ops: int = 4096):
+        """kbhip_walk_victims_from: one window (up to 64 entries) of the
+        task's eviction walk behind a resume point: (ops[n], pods[n], nodes[n],
+        info), ready for apply_ops.  after: None (from the top), or
+        (resume_node, resume_score) of the call to go on from — after a
+        WALK_HEAD_END or WALK_CAPACITY stop, with the ops applied in between.
+        info: {"stop" (a WALK_* reason), "remaining" (walk entries behind the
+        resume point at the call), "visited", "acted", "resume_node",
+        "resume_score", "launches", "rebuilt", "state_rebuilt", "patched",
+        "last_node", "first_valid"}."""
+        cap_ops = int(cap_ops)
+        room = max(cap_ops, 1)
+        op, pod, node = np.zeros(room, np.uint8), np.full(room, -1, np.int32), np.full(room, -1, np.int32)
+        info = np.zeros(10, np.int64)
+        a_node, a_score = (-1, 0) if after is None else (int(after[0]), int(after[1]))
+        n = int(lib().kbhip_walk_victims_from(self._h, int(task_id), int(by_score), int(victims), int(cap), a_node,
+                                              a_score, _p(op), _p(pod), _p(node), cap_ops, _p(info)))
+        _check(n if n < 0 else 0)
+        return op[:n].copy(), pod[:n].copy(), node[:n].copy(), _walk_from_info(info)
 
     def explain_tasks(self, task_ids, verdicts: bool = False, n_nodes: Optional[int] = None):
         """kbhip_explain_tasks: why each node is, or is not, in the allocate
