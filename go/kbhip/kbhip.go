@@ -388,6 +388,17 @@ type HeadVictimsInfo struct {
 	MaxCount     int64 // the largest Count: a stride below it truncated a row
 }
 
+// headVictimAt is head entry `at` of the calls' output arrays (victim rows of stride words).
+func headVictimAt(nodes, scores, counts, evicts []int32, flags []uint8, rows []int32, at, stride int) HeadVictim {
+	n := int(counts[at])
+	if n > stride {
+		n = stride
+	}
+	lo := at * stride
+	return HeadVictim{Node: nodes[at], Score: scores[at], Count: counts[at], Evict: evicts[at], Flags: flags[at],
+		Victims: rows[lo : lo+n : lo+n]}
+}
+
 // HeadVictims answers the head of RankVictimNodes' walk together with the
 // victim decision on each head node (kbhip_head_victims): the step of a
 // reclaim / preempt loop between the ranking and ApplyOps.  1 <= cap <= 64,
@@ -417,13 +428,7 @@ func (e *Engine) HeadVictims(task int32, byScore bool, victims int32, cap, strid
 	}
 	heads = make([]HeadVictim, k)
 	for i := range heads {
-		n := int(counts[i])
-		if n > stride {
-			n = stride
-		}
-		lo := i * stride
-		heads[i] = HeadVictim{Node: nodes[i], Score: scores[i], Count: counts[i], Evict: evicts[i], Flags: flags[i],
-			Victims: rows[lo : lo+n : lo+n]}
+		heads[i] = headVictimAt(nodes, scores, counts, evicts, flags, rows, i, stride)
 	}
 	return int64(t), heads, info, nil
 }
@@ -487,14 +492,7 @@ func (e *Engine) HeadsVictims(tasks []int32, byScore bool, victims int32, cap, s
 		}
 		heads := make([]HeadVictim, k)
 		for i := range heads {
-			at := t*cap + i
-			c := int(counts[at])
-			if c > stride {
-				c = stride
-			}
-			lo := at * stride
-			heads[i] = HeadVictim{Node: nodes[at], Score: scores[at], Count: counts[at], Evict: evicts[at],
-				Flags: flags[at], Victims: rows[lo : lo+c : lo+c]}
+			heads[i] = headVictimAt(nodes, scores, counts, evicts, flags, rows, t*cap+i, stride)
 		}
 		out[t] = TaskHeadVictims{Total: total[t], First: first[t], Heads: heads}
 	}

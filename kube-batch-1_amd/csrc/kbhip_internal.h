@@ -327,7 +327,7 @@ hipError_t launch_walk_victims(const VictState& st, const VictHdr& h, const uint
 // (head_victims_row with no victim row), flags[3 i ..] = entry i's count, evict, flags; lds_recs and spill
 // (cap rows) as launch_heads_victims.  k_walk_victims_from: one block; the entries before the first VALID
 // one are passed over by their flag (no eviction precedes them, so the flag is the walk's answer), from it
-// on k_walk_victims' loop.  out_info (10 int64): stop, total, visited, acted, the resume point's node and
+// on the loop k_walk_victims runs.  out_info (10 int64): stop, total, visited, acted, the resume point's node and
 // score (-1, 0: no entry was passed over or acted on), ops, the resume point's window index (-1), the last
 // acted-on node (-1), the first VALID entry's window index (-1).
 hipError_t launch_walk_victims_from(const VictState& st, const VictHdr& h, const uint64_t* head, int cap, int task,

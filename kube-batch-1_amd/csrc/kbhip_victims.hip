@@ -30,12 +30,13 @@
 //                    state's longest node.
 //   k_walk_victims   kbhip_walk_victims: one block walks the head entries in
 //                    order, staging each node as above under an overlay of
-//                    the evictions of the entries before it (described at the
-//                    kernel).
+//                    the evictions of the entries before it (walk_loop over
+//                    walk_entry, described there).
 //   k_walk_flags, k_walk_victims_from
 //                    kbhip_walk_victims_from: the entries of a window behind
 //                    the caller's resume point decided side by side (flags
-//                    only), then the walk from the first entry that can act.
+//                    only), then the same walk_loop from the first entry that
+//                    can act.
 //   k_victims_patch  the records kbhip_apply_ops left dirty, one thread each.
 // Stores are plain vector stores; nothing is atomic, no block waits for another.
 #include <hip/hip_runtime.h>
@@ -44,6 +45,18 @@
 #include "kbhip_internal.h"
 
 namespace kbhip {
+
+// The task records of a head key's node: off, n.  False: the key names no node of the state, or records
+// outside the state, or more than lds_cap staged records or a spill row of spill_stride (null: none) hold.
+// What false means is the caller's: "no node" to head_victims_row, a visit that stages nothing to the walk.
+__device__ __forceinline__ bool head_node_range(const VictState& st, uint64_t key, int node_base, int lds_cap,
+                                                const VictRec* spill, int spill_stride, int& off, int& n) {
+    const int node = key_idx(key) - node_base;
+    if (key == 0 || node < 0 || node >= st.n_nodes) return false;
+    off = st.node_off[node];
+    n = st.node_off[node + 1] - off;
+    return off >= 0 && n >= 0 && off + n <= st.n_tasks && (n <= lds_cap || (spill && n <= spill_stride));
+}
 
 // Head entry i of `head` (the keys, then the count) decided into `row` (count, evict, flags, then stride
 // victims), by one wave: what k_head_victims and k_heads_victims run per block.  lds: room for lds_cap
@@ -54,13 +67,9 @@ __device__ __forceinline__ void head_victims_row(const VictState& st, const Vict
                                                  VictRec* spill_row, int spill_stride, int32_t* row) {
     const int lane = threadIdx.x;
     const uint64_t key = head[i], total = head[kTopK];
-    const int node = key_idx(key) - node_base;
-    int off = 0, n = -1;  // n < 0: no node in this row
-    if ((uint64_t)i < total && key != 0 && node >= 0 && node < st.n_nodes) {
-        off = st.node_off[node];
-        n = st.node_off[node + 1] - off;
-        if (off < 0 || n < 0 || off + n > st.n_tasks || (n > lds_cap && (!spill_row || n > spill_stride))) n = -1;
-    }
+    int off = 0, n;
+    const bool in = ((uint64_t)i < total) & (key != 0);  // (&: the key's and the count's loads are in flight together)
+    if (!in || !head_node_range(st, key, node_base, lds_cap, spill_row, spill_stride, off, n)) n = -1;  // no node
     int count = 0;
     if (n > 0) {  // (uniform over the block)
         VictRec* const rec = n <= lds_cap ? lds : spill_row;
@@ -140,62 +149,81 @@ __global__ __launch_bounds__(256) void k_victims_patch(VictTask* task, VictJob* 
     }
 }
 
-// kbhip_walk_victims: the node loop of one task over the head, one block of kWalkBlock threads.  The loop
-// over the head entries is sequential by its definition (entry i + 1 reads what entry i evicted); inside
-// an entry the threads stage and link the node's records under the overlay, thread 0 runs walk_step (the
-// decision, the ops, the fold: the evicted prefix is a few tasks, and the fold keeps the job's entries in
-// victim order), and a barrier hands the overlay to the next entry.  Records, overlay, header and progress
-// live in LDS (43 KB + 9 KB); nothing is prefetched for the next entry while thread 0 decides.
+// The eviction walk of one task, one block of kWalkBlock threads: what k_walk_victims and
+// k_walk_victims_from share.  The loop over the entries is sequential by its definition (entry i + 1 reads
+// what entry i evicted); inside an entry the threads stage and link the node's records under the overlay,
+// thread 0 runs walk_step (the decision, the ops, the fold: the evicted prefix is a few tasks, and the fold
+// keeps the job's entries in victim order), and a barrier hands the overlay to the next entry.  Records,
+// overlay, header and progress live in LDS (43 KB + 9 KB); nothing is prefetched for the next entry while
+// thread 0 decides.
 constexpr int kWalkBlock = 256;
+struct WalkLds { VictRec rec[kVictLds]; WalkOverlay ov; VictHdr h; WalkCtl c; };
+struct WalkArgs { int node_base; VictRec* spill; int spill_stride; int32_t *out_pod, *out_node; };  // as the kernels'
+
+// Entry i, by the whole block.  A key without a node, or whose node can be staged nowhere, stages nothing
+// and is still visited.  res (k_walk_victims_from; else null): *res = i unless the entry was refused with
+// kWalkCapacity.  Every thread reads walk_step's result behind the last barrier.
+__device__ __forceinline__ void walk_entry(const VictState& st, WalkLds& s, const WalkArgs& a, uint64_t key, int i,
+                                           int* res) {
+    const int tid = threadIdx.x;
+    int off = 0, n;
+    if (!head_node_range(st, key, a.node_base, kVictLds, a.spill, a.spill_stride, off, n)) n = 0;
+    VictRec* const rec = n <= kVictLds ? s.rec : a.spill;
+    for (int k = tid; k < n; k += kWalkBlock) vict_stage_walk(st, s.h, s.ov, off + k, rec[k]);
+    __syncthreads();
+    for (int k = tid; k < n; k += kWalkBlock) vict_link(rec, k);
+    __syncthreads();
+    if (tid == 0) {
+        const int acted = s.c.acted;
+        walk_step(s.h, s.ov, s.c, rec, n, key_idx(key), key_score(key), a.out_pod, a.out_node);
+        if (res && (s.c.stop != kWalkCapacity || s.c.acted != acted)) *res = i;  // passed over or acted on
+    }
+    __syncthreads();
+}
+
+// Entries [i, lim) of `head` in order until one stops the walk, then out_info[0 .. 3] and [6]: the stop reason,
+// the head's count, the visits, the nodes acted on, the ops.  kHead (k_walk_victims): at most `cap` visits, and
+// an entry whose key is not below after_key (0: none) is left out.  (Every condition is uniform over the block.)
+template <bool kHead>
+__device__ __forceinline__ void walk_loop(const VictState& st, WalkLds& s, const WalkArgs& a, const uint64_t* head,
+                                          int i, int lim, int cap, uint64_t after_key, int* res, int64_t* out_info) {
+    for (; i < lim; ++i) {
+        if (kHead && s.c.visited >= cap) break;
+        const uint64_t key = head[i];
+        if (kHead && after_key != 0 && key >= after_key) continue;
+        walk_entry(st, s, a, key, i, res);
+        if (s.c.stop != 0) break;
+    }
+    if (threadIdx.x != 0) return;
+    const uint64_t total = head[kTopK];
+    out_info[0] = s.c.stop != 0 ? s.c.stop : (uint64_t)i < total ? kWalkHeadEnd : kWalkExhausted;
+    out_info[1] = (int64_t)total;
+    out_info[2] = s.c.visited;
+    out_info[3] = s.c.acted;
+    out_info[6] = s.c.n_ops;
+}
+
+// kbhip_walk_victims: the walk over the head from its top.
 __global__ __launch_bounds__(kWalkBlock) void k_walk_victims(VictState st, VictHdr h0, const uint64_t* head, int cap,
                                                              uint64_t after_key, int task, int node_base,
                                                              VictRec* spill, int spill_stride, int ov_cap_j,
                                                              int ov_cap_q, int64_t cap_ops, int64_t* out_info,
                                                              int32_t* out_pod, int32_t* out_node) {
-    __shared__ VictRec s_rec[kVictLds];
-    __shared__ WalkOverlay s_ov;
-    __shared__ VictHdr s_h;
-    __shared__ WalkCtl s_c;
+    __shared__ WalkLds s;
     const int tid = threadIdx.x;
     if (tid == 0) {
-        s_h = h0;
-        walk_ov_init(s_ov, ov_cap_j, ov_cap_q);
-        s_c = WalkCtl{0, cap_ops, 0, 0, 0, -1, 0, task};
+        s.h = h0;
+        walk_ov_init(s.ov, ov_cap_j, ov_cap_q);
+        s.c = WalkCtl{0, cap_ops, 0, 0, 0, -1, 0, task};
     }
     __syncthreads();
     const uint64_t total = head[kTopK];
     const int in_head = total < (uint64_t)kTopK ? (int)total : kTopK;
-    int i = 0;
-    for (; i < in_head; ++i) {  // (every condition below is uniform over the block)
-        if (s_c.visited >= cap) break;
-        const uint64_t key = head[i];
-        if (after_key != 0 && key >= after_key) continue;  // the loop has left this node behind
-        const int node = key_idx(key) - node_base;
-        int off = 0, n = 0;  // n == 0: nothing to stage (walk_step still counts the visit)
-        if (key != 0 && node >= 0 && node < st.n_nodes) {
-            off = st.node_off[node];
-            n = st.node_off[node + 1] - off;
-            if (off < 0 || n < 0 || off + n > st.n_tasks || (n > kVictLds && (!spill || n > spill_stride))) n = 0;
-        }
-        VictRec* const rec = n <= kVictLds ? s_rec : spill;
-        for (int k = tid; k < n; k += kWalkBlock) vict_stage_walk(st, s_h, s_ov, off + k, rec[k]);
-        __syncthreads();
-        for (int k = tid; k < n; k += kWalkBlock) vict_link(rec, k);
-        __syncthreads();
-        if (tid == 0) walk_step(s_h, s_ov, s_c, rec, n, key_idx(key), key_score(key), out_pod, out_node);
-        __syncthreads();
-        if (s_c.stop != 0) break;
-    }
+    walk_loop<true>(st, s, WalkArgs{node_base, spill, spill_stride, out_pod, out_node}, head, 0, in_head, cap,
+                    after_key, nullptr, out_info);
     if (tid == 0) {
-        int stop = s_c.stop;
-        if (stop == 0) stop = (uint64_t)i < total ? kWalkHeadEnd : kWalkExhausted;
-        out_info[0] = stop;
-        out_info[1] = (int64_t)total;
-        out_info[2] = s_c.visited;
-        out_info[3] = s_c.acted;
-        out_info[4] = s_c.last_node;
-        out_info[5] = s_c.last_score;
-        out_info[6] = s_c.n_ops;
+        out_info[4] = s.c.last_node;
+        out_info[5] = s.c.last_score;
         out_info[7] = 0;
     }
 }
@@ -212,24 +240,21 @@ __global__ __launch_bounds__(64) void k_walk_flags(VictState st, VictHdr h, cons
                      spill ? spill + (size_t)i * spill_stride : nullptr, spill_stride, flags + 3 * i);
 }
 
-// kbhip_walk_victims_from, the walk: k_walk_victims over a window every entry of which is behind the
+// kbhip_walk_victims_from, the walk: the same loop over a window every entry of which is behind the
 // caller's resume point (the bounded sweep left the others out), so no entry is skipped by its key and an
-// entry's window index is the number of entries decided before it.  The entries before the first one the
-// pre-pass found VALID (a ballot over the flag words) are passed over without staging: no eviction
-// precedes them, so the overlay is empty and the stateless flag is the walk's answer.  From that entry on
-// the loop is k_walk_victims' — that entry too is decided by walk_step, and the entries after it never by
-// their flag: carried state can turn an invalid node valid.  s_res: the window index of the resume point,
-// the last entry passed over or acted on (an entry refused with kWalkCapacity is met again by the next call).
+// entry's window index is the number of entries decided before it: `lim` bounds the visits.  The entries
+// before the first one the pre-pass found VALID (a ballot over the flag words) are passed over without
+// staging: no eviction precedes them, so the overlay is empty and the stateless flag is the walk's answer.
+// The loop starts at that entry — it too is decided by walk_step, and the entries after it never by their
+// flag: carried state can turn an invalid node valid.  s_res: the window index of the resume point, the
+// last entry passed over or acted on (an entry refused with kWalkCapacity is met again by the next call).
 __global__ __launch_bounds__(kWalkBlock) void k_walk_victims_from(VictState st, VictHdr h0, const uint64_t* head,
                                                                   int cap, const int32_t* flags, int task,
                                                                   int node_base, VictRec* spill, int spill_stride,
                                                                   int ov_cap_j, int ov_cap_q, int64_t cap_ops,
                                                                   int64_t* out_info, int32_t* out_pod,
                                                                   int32_t* out_node) {
-    __shared__ VictRec s_rec[kVictLds];
-    __shared__ WalkOverlay s_ov;
-    __shared__ VictHdr s_h;
-    __shared__ WalkCtl s_c;
+    __shared__ WalkLds s;
     __shared__ int s_first, s_res;
     const int tid = threadIdx.x;
     const uint64_t total = head[kTopK];
@@ -242,48 +267,20 @@ __global__ __launch_bounds__(kWalkBlock) void k_walk_victims_from(VictState st, 
             const int passed = first < 0 ? lim : first;
             s_first = first;
             s_res = passed - 1;
-            s_h = h0;
-            walk_ov_init(s_ov, ov_cap_j, ov_cap_q);
-            s_c = WalkCtl{0, cap_ops, 0, passed, 0, -1, 0, task};
+            s.h = h0;
+            walk_ov_init(s.ov, ov_cap_j, ov_cap_q);
+            s.c = WalkCtl{0, cap_ops, 0, passed, 0, -1, 0, task};
         }
     }
     __syncthreads();
-    int i = s_first < 0 ? lim : s_first;
-    for (; i < lim; ++i) {  // (every condition below is uniform over the block)
-        const uint64_t key = head[i];
-        const int node = key_idx(key) - node_base;
-        int off = 0, n = 0;  // n == 0: nothing to stage (walk_step still counts the visit)
-        if (key != 0 && node >= 0 && node < st.n_nodes) {
-            off = st.node_off[node];
-            n = st.node_off[node + 1] - off;
-            if (off < 0 || n < 0 || off + n > st.n_tasks || (n > kVictLds && (!spill || n > spill_stride))) n = 0;
-        }
-        VictRec* const rec = n <= kVictLds ? s_rec : spill;
-        for (int k = tid; k < n; k += kWalkBlock) vict_stage_walk(st, s_h, s_ov, off + k, rec[k]);
-        __syncthreads();
-        for (int k = tid; k < n; k += kWalkBlock) vict_link(rec, k);
-        __syncthreads();
-        if (tid == 0) {
-            const int acted = s_c.acted;
-            walk_step(s_h, s_ov, s_c, rec, n, key_idx(key), key_score(key), out_pod, out_node);
-            if (s_c.stop != kWalkCapacity || s_c.acted != acted) s_res = i;  // passed over or acted on
-        }
-        __syncthreads();
-        if (s_c.stop != 0) break;
-    }
+    walk_loop<false>(st, s, WalkArgs{node_base, spill, spill_stride, out_pod, out_node}, head,
+                     s_first < 0 ? lim : s_first, lim, cap, 0, &s_res, out_info);
     if (tid == 0) {
-        int stop = s_c.stop;
-        if (stop == 0) stop = (uint64_t)i < total ? kWalkHeadEnd : kWalkExhausted;
         const int res = s_res;
-        out_info[0] = stop;
-        out_info[1] = (int64_t)total;
-        out_info[2] = s_c.visited;
-        out_info[3] = s_c.acted;
         out_info[4] = res >= 0 ? key_idx(head[res]) : -1;
         out_info[5] = res >= 0 ? key_score(head[res]) : 0;
-        out_info[6] = s_c.n_ops;
         out_info[7] = res;
-        out_info[8] = s_c.last_node;
+        out_info[8] = s.c.last_node;
         out_info[9] = s_first;
     }
 }

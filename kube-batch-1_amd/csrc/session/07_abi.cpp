@@ -491,7 +491,7 @@ int64_t kbhip_debug_table(kb_session* s, const char* name, void* out, int64_t ca
             for (size_t i = 0; i < S.pods.size(); ++i) v[i] = n == "pod_status" ? S.pods[i].status : S.pods[i].node;
         } else if (n == "dims") {  // n_nodes, npad, n_spaces, n_classes
             v = {S.nc.n, S.nc.npad, S.n_spaces, (int32_t)S.classes.size()};
-        } else {  // the plugin state the victim functions read (15_victims.cpp)
+        } else {  // the plugin state the victim functions read (18_victim_state.cpp)
             vector<uint8_t> raw;
             if (!kbhip::debug_victim_table(s->s, n, raw)) throw kbhip::Error(KBHIP_EINVAL, "unknown table " + n);
             if (out && cap_bytes >= (int64_t)raw.size() && !raw.empty()) std::memcpy(out, raw.data(), raw.size());

@@ -261,7 +261,7 @@ int64_t kbhip_rank_nodes(kb_session* s, int32_t task_id, int32_t by_score, int64
     ABI_GUARD_S(s, {
         if (first < 0 || cap < 0 || (cap > 0 && !out_node))
             throw kbhip::Error(KBHIP_EINVAL, "kbhip_rank_nodes: negative first or cap, or null out_node with cap > 0");
-        if (by_score != 0 && by_score != 1) throw kbhip::Error(KBHIP_EINVAL, "kbhip_rank_nodes: by_score is 0 or 1");
+        check_by_score("kbhip_rank_nodes", by_score);
         return kbhip::rank_victim_nodes_abi(kbhip::device_session(s), task_id, by_score != 0, 0, first, out_node,
                                             out_score, nullptr, cap, nullptr);
     })
@@ -274,10 +274,8 @@ int64_t kbhip_rank_victim_nodes(kb_session* s, int32_t task_id, int32_t by_score
         if (first < 0 || cap < 0 || (cap > 0 && !out_node))
             throw kbhip::Error(KBHIP_EINVAL,
                                "kbhip_rank_victim_nodes: negative first or cap, or null out_node with cap > 0");
-        if (by_score != 0 && by_score != 1)
-            throw kbhip::Error(KBHIP_EINVAL, "kbhip_rank_victim_nodes: by_score is 0 or 1");
-        if (victims < KBHIP_VICTIMS_OTHER_QUEUES || victims > KBHIP_VICTIMS_SAME_JOB)
-            throw kbhip::Error(KBHIP_EINVAL, "kbhip_rank_victim_nodes: victims is one of KBHIP_VICTIMS_* (1..3)");
+        check_by_score("kbhip_rank_victim_nodes", by_score);
+        check_victims("kbhip_rank_victim_nodes", victims);
         return kbhip::rank_victim_nodes_abi(kbhip::device_session(s), task_id, by_score != 0, victims, first, out_node,
                                             out_score, out_cands, cap, out_info);
     })

@@ -178,10 +178,9 @@ int64_t kbhip_rank_heads(kb_session* s, const int32_t* task_ids, int32_t n_tasks
     ABI_GUARD_S(s, {
         if (n_tasks < 0 || n_tasks > KBHIP_RANK_HEADS_MAX)
             throw kbhip::Error(KBHIP_EINVAL, "kbhip_rank_heads: n_tasks is 0 .. KBHIP_RANK_HEADS_MAX (64)");
-        if (cap < 1 || cap > 64) throw kbhip::Error(KBHIP_EINVAL, "kbhip_rank_heads: cap is 1 .. 64");
-        if (by_score != 0 && by_score != 1) throw kbhip::Error(KBHIP_EINVAL, "kbhip_rank_heads: by_score is 0 or 1");
-        if (victims < 0 || victims > KBHIP_VICTIMS_SAME_JOB)
-            throw kbhip::Error(KBHIP_EINVAL, "kbhip_rank_heads: victims is 0 or one of KBHIP_VICTIMS_* (1..3)");
+        check_cap("kbhip_rank_heads", cap);
+        check_by_score("kbhip_rank_heads", by_score);
+        check_victims("kbhip_rank_heads", victims, true);
         if (!task_ids || !out_total || !out_node)
             throw kbhip::Error(KBHIP_EINVAL, "kbhip_rank_heads: null task_ids, out_total or out_node");
         kbhip::Session& S = kbhip::device_session(s);

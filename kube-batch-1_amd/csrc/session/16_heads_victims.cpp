@@ -51,8 +51,7 @@ int64_t heads_victims_abi(Session& S, const int32_t* task_ids, int n, bool by_sc
     for (int r0 = 0; r0 < n; r0 += per_range) {
         const int nr = std::min(per_range, n - r0);
         HIPCHK(launch_heads_victims(st, (const VictHdr*)B.d_extra + r0, (const uint64_t*)S.b_heads.p + r0 * key_words,
-                                    nr, cap, dstride, S.nc.base, std::min(kVictLds, std::max(S.vs_max_tasks, 1)),
-                                    spill ? (VictRec*)S.b_vs_spill.p : nullptr, spill ? S.vs_max_tasks : 0,
+                                    nr, cap, dstride, S.nc.base, vs_lds_recs(S), vs_spill_rows(S), vs_spill_stride(S),
                                     (uint64_t*)d_out + r0 * key_words,
                                     (int32_t*)(d_out + key_bytes) + (size_t)r0 * cap * row_words, S.stream));
         vict_launches += 1;
@@ -76,14 +75,8 @@ int64_t heads_victims_abi(Session& S, const int32_t* task_ids, int n, bool by_sc
         for (int k = cap - 1; k >= 0; --k)
             if (out_flags[at + k] & KBHIP_HEAD_VICTIMS_VALID) out_first[i] = k;
     }
-    if (out_info) {
-        out_info[0] = vp.rebuilt ? 1 : 0;
-        out_info[1] = vp.vs_rebuilt ? 1 : 0;
-        out_info[2] = vp.patched;
-        out_info[3] = launches;
-        out_info[4] = max_count;
-        out_info[5] = vict_launches;
-    }
+    head_info_fill(out_info, vp, launches, max_count);
+    if (out_info) out_info[5] = vict_launches;
     S.stats.rank_heads += n;
     S.stats.sweeps += n;
     return n;
@@ -102,12 +95,10 @@ int64_t kbhip_heads_victims(kb_session* s, const int32_t* task_ids, int32_t n_ta
     ABI_GUARD_S(s, {
         if (n_tasks < 0 || n_tasks > KBHIP_HEADS_VICTIMS_MAX)
             throw kbhip::Error(KBHIP_EINVAL, "kbhip_heads_victims: n_tasks is 0 .. KBHIP_HEADS_VICTIMS_MAX (64)");
-        if (cap < 1 || cap > 64) throw kbhip::Error(KBHIP_EINVAL, "kbhip_heads_victims: cap is 1 .. 64");
-        if (stride < 1) throw kbhip::Error(KBHIP_EINVAL, "kbhip_heads_victims: stride is at least 1");
-        if (by_score != 0 && by_score != 1)
-            throw kbhip::Error(KBHIP_EINVAL, "kbhip_heads_victims: by_score is 0 or 1");
-        if (victims < KBHIP_VICTIMS_OTHER_QUEUES || victims > KBHIP_VICTIMS_SAME_JOB)
-            throw kbhip::Error(KBHIP_EINVAL, "kbhip_heads_victims: victims is one of KBHIP_VICTIMS_* (1..3)");
+        check_cap("kbhip_heads_victims", cap);
+        check_stride("kbhip_heads_victims", stride);
+        check_by_score("kbhip_heads_victims", by_score);
+        check_victims("kbhip_heads_victims", victims);
         if (!task_ids || !out_total || !out_node || !out_count || !out_evict || !out_flags || !out_victim)
             throw kbhip::Error(KBHIP_EINVAL, "kbhip_heads_victims: null task_ids, out_total, out_node, out_count, "
                                              "out_evict, out_flags or out_victim");

@@ -13,7 +13,11 @@
 // 11_evict (the reclaim / preempt actions and the device ranking of a task's
 // nodes), 12_rank (the walk window of one task: kbhip_rank_nodes,
 // kbhip_rank_victim_nodes and the victim-candidate table), 13_heads
-// (kbhip_rank_heads), 14_explain (kbhip_explain_tasks).  buffers.h holds DevBuf
+// (kbhip_rank_heads), 14_explain (kbhip_explain_tasks), 15_victims
+// (kbhip_head_victims and the preparation the victim queries share),
+// 16_heads_victims (kbhip_heads_victims), 17_walk_victims (kbhip_walk_victims,
+// kbhip_walk_victims_from), 18_victim_state (the victim state they read: build,
+// upload, patch).  buffers.h holds DevBuf
 // and PinnedBuf, the holders of pooled device and pinned memory.  framework.h, which
 // the parts running actions include, is the C++ mirror of the Go framework they
 // share: the heaps, the ordering plugins, the status index, the statements.
@@ -613,7 +617,7 @@ struct Session {
     bool vict_live = false;
     DevBuf b_vict, b_vict_own, b_vict_blk, b_vict_keys, b_vict_cands;
     PinnedBuf h_vict_own, h_vict_out;
-    // kbhip_head_victims (15_victims.cpp): the victim state (VictState, kbhip_internal.h) on the device.
+    // kbhip_head_victims (18_victim_state.cpp): the victim state (VictState, kbhip_internal.h) on the device.
     // vs_live: it is current — built from the host model by the first call that needs it, cleared wherever
     // vict_live is (vict_stale).  kbhip_apply_ops does not clear it: it appends the pods, jobs and queues it
     // touched to vs_dirty_*, and the next kbhip_head_victims uploads those records and scatters them in one
@@ -629,7 +633,7 @@ struct Session {
     double vs_build_s = 0;
     DevBuf b_vs_off, b_vs_task, b_vs_job, b_vs_queue, b_vs_spill, b_vs_patch, b_vs_out;
     PinnedBuf h_vs_patch, h_vs_out;
-    struct VictHost;  // the state on the host (15_victims.cpp)
+    struct VictHost;  // the state on the host (defined with vs_build_host's declaration; 18_victim_state.cpp fills it)
     // kbhip_walk_victims: option "walk_overlay_max" (tests; 0 = the full overlay): the touched jobs and the
     // touched queues a walk carries at most
     int32_t walk_ov_max = 0;
@@ -1238,7 +1242,7 @@ const HPod& query_task(const Session& S, int pod, const string& prefix, bool nee
 void query_begin(Session& S, const char* api_name);
 // kbhip_rank_victim_nodes (12_rank.cpp).  vict_stale: the call that follows changes pod statuses outside
 // kbhip_apply_ops — the victim-candidate table is rebuilt by the next ranking that needs it.
-// The victim state of kbhip_head_victims (15_victims.cpp) goes stale with it, and its dirty lists end.
+// The victim state of kbhip_head_victims (18_victim_state.cpp) goes stale with it, and its dirty lists end.
 inline void vict_stale(Session& S) {
     S.vict_live = false;
     S.vs_live = false;
@@ -1296,21 +1300,45 @@ int64_t apply_ops(Session& S, const uint8_t* op, const int32_t* pod, const int32
 int64_t explain_tasks_abi(Session& S, const int32_t* task_ids, int n_tasks, uint8_t* out_verdict, int64_t* out_hist,
                           int64_t* out_info);
 void debug_explain(const Session& S, int pod, uint8_t* out_verdict, int64_t* out_hist);
-// kbhip_head_victims (15_victims.cpp).  vs_mark_dirty: a batch of kbhip_apply_ops that reached the host
-// model (a live state only).  debug_victim_table: kbhip_debug_table's plugin-state tables; false: not one.
+// kbhip_head_victims (15_victims.cpp).  vs_mark_dirty (18_victim_state.cpp): a batch of kbhip_apply_ops that
+// reached the host model (a live state only).  debug_victim_table: kbhip_debug_table's plugin-state tables;
+// false: not one.
 int64_t head_victims_abi(Session& S, int pod, bool by_score, int mode, int cap, int stride, int32_t* out_node,
                          int32_t* out_score, int32_t* out_count, int32_t* out_evict, uint8_t* out_flags,
                          int32_t* out_victim, int64_t* out_info);
 void vs_mark_dirty(Session& S, const int32_t* pod, int64_t n);
+// The victim state (18_victim_state.cpp): built on the host (plugins opened), built and uploaded, its dirty
+// records patched by one launch (returns their number).  The accessors: what a victim kernel launch takes
+// from it — the spill rows and their stride (null, 0: no node above kVictLds), the records staged in LDS.
+struct Session::VictHost {  // the victim state on the host (VictState, kbhip_internal.h)
+    vector<int32_t> node_off, pos;
+    vector<VictTask> task;
+    vector<VictJob> job;
+    vector<VictQueue> queue;
+    int32_t max_tasks = 0;
+    VictState view(const Session& S) const {
+        return VictState{node_off.data(), task.data(), job.data(), queue.data(), S.n_total, (int32_t)job.size(),
+                         (int32_t)queue.size(), (int32_t)task.size()};
+    }
+};
+void vs_build_host(const Session& S, Session::VictHost& H);
+void vs_build(Session& S, int batch_rows);
+int64_t vs_patch(Session& S);
+inline VictRec* vs_spill_rows(const Session& S) { return S.vs_max_tasks > kVictLds ? (VictRec*)S.b_vs_spill.p : nullptr; }
+inline int vs_spill_stride(const Session& S) { return S.vs_max_tasks > kVictLds ? S.vs_max_tasks : 0; }
+inline int vs_lds_recs(const Session& S) { return std::min(kVictLds, std::max(S.vs_max_tasks, 1)); }
+// the walk overlay's capacities in force (option "walk_overlay_max"; 0: the full overlay)
+inline int walk_ov_jobs(const Session& S) { return S.walk_ov_max > 0 ? S.walk_ov_max : kWalkOvJobs; }
+inline int walk_ov_queues(const Session& S) { return S.walk_ov_max > 0 ? S.walk_ov_max : kWalkOvQueues; }
 // What kbhip_head_victims, kbhip_walk_victims and kbhip_heads_victims (16_heads_victims.cpp) share.
 // make_hdr: one request's constants (KBHIP_EUNSUPPORTED above kVictMaxCodes).  vict_prepare, with the
 // plugins open: both tables made current — built, or the dirty records patched in one launch — and the
 // pending count-table changes flushed; batch_rows > 0 (a batched call of that many rows per request):
 // vs_spill_check on a state built here, before anything of it is uploaded.  vs_spill_check: refuses
 // (KBHIP_EUNSUPPORTED) where `rows` spill rows of a state whose longest node has max_tasks tasks exceed
-// option "victims_spill_max".  vs_device_view: the device state.  head_rows_unpack: one request's keys and
-// device rows (3 + dstride words each) written to the ABI's arrays of cap entries (victim rows of stride,
-// the tail beyond dstride -1); returns the largest count.
+// option "victims_spill_max".  head_rows_unpack: one request's keys and device rows (3 + dstride words each)
+// written to the ABI's arrays of cap entries (victim rows of stride, the tail beyond dstride -1); returns
+// the largest count.  head_info_fill: out_info[0 .. 4] of both head calls (null: nothing).
 struct VictPrep {
     bool rebuilt, vs_rebuilt;
     int64_t patched, launches;
@@ -1322,6 +1350,7 @@ VictState vs_device_view(const Session& S);
 int64_t head_rows_unpack(const uint64_t* keys, const int32_t* rows, int cap, int stride, int dstride, bool by_score,
                          int32_t* out_node, int32_t* out_score, int32_t* out_count, int32_t* out_evict,
                          uint8_t* out_flags, int32_t* out_victim);
+void head_info_fill(int64_t* out_info, const VictPrep& vp, int64_t launches, int64_t max_count);
 int64_t heads_victims_abi(Session& S, const int32_t* task_ids, int n_tasks, bool by_score, int mode, int cap,
                           int stride, int64_t* out_total, int32_t* out_node, int32_t* out_score, int32_t* out_count,
                           int32_t* out_evict, uint8_t* out_flags, int32_t* out_victim, int32_t* out_first,
@@ -1329,8 +1358,8 @@ int64_t heads_victims_abi(Session& S, const int32_t* task_ids, int n_tasks, bool
 void debug_victims(Session& S, int pod, int mode, int node, int stride, int32_t* out_count, int32_t* out_evict,
                    uint8_t* out_flags, int32_t* out_victim);
 bool debug_victim_table(Session& S, const string& name, vector<uint8_t>& out);
-// kbhip_walk_victims / kbhip_debug_walk_victims (15_victims.cpp): one task's eviction walk, on the head and
-// over a caller's node list on the host tables
+// kbhip_walk_victims / kbhip_debug_walk_victims (17_walk_victims.cpp): one task's eviction walk, on the head
+// and over a caller's node list on the host tables
 int64_t walk_victims_abi(Session& S, int pod, bool by_score, int mode, int cap, int after_node, int after_score,
                          uint8_t* out_op, int32_t* out_pod, int32_t* out_node, int64_t cap_ops, int64_t* out_info);
 int64_t debug_walk_victims(Session& S, int pod, int mode, const int32_t* nodes, int n_nodes, int64_t cap_ops,
@@ -1342,16 +1371,16 @@ int64_t debug_walk_victims(Session& S, int pod, int mode, const int32_t* nodes, 
 // the nodes whose key is below bound.
 VictArgs vict_args(Session& S, const HPod& p, int mode, vector<int32_t>& own_node, vector<int64_t>& own_sum);
 int rank_head_enqueue(Session& S, int cls, bool by_score, const VictArgs* v, uint64_t bound = 0);
-// What kbhip_head_victims, kbhip_walk_victims (15_victims.cpp) and kbhip_walk_victims_from
-// (17_walk_from.cpp) do before their own kernel: the plugins opened, the call's header, vict_prepare and
-// rank_head_enqueue in a victim mode.
+// What kbhip_head_victims (15_victims.cpp), kbhip_walk_victims and kbhip_walk_victims_from
+// (17_walk_victims.cpp) do before their own kernel: the plugins opened, the call's header, vict_prepare and
+// rank_head_enqueue in a victim mode (launches: of both).
 struct HeadPrep {
     VictHdr h;
-    bool rebuilt, vs_rebuilt;
-    int64_t patched, launches;
+    VictPrep vp;
+    int64_t launches;
 };
 HeadPrep head_prepare(Session& S, const HPod& p, bool by_score, int mode, uint64_t bound = 0);
-// kbhip_walk_victims_from (17_walk_from.cpp): one window of a task's eviction walk behind a resume point
+// kbhip_walk_victims_from (17_walk_victims.cpp): one window of a task's eviction walk behind a resume point
 int64_t walk_victims_from_abi(Session& S, int pod, bool by_score, int mode, int cap, int after_node, int after_score,
                               uint8_t* out_op, int32_t* out_pod, int32_t* out_node, int64_t cap_ops,
                               int64_t* out_info);
@@ -1399,6 +1428,21 @@ inline void check_log_args(kb_session* s, const int32_t* out_pod, const int32_t*
     if (cap < 0 || (cap > 0 && (!out_pod || !out_node || !out_kind)))
         throw kbhip::Error(KBHIP_EINVAL, "null output array with cap > 0");
 }
+
+// The refusals the task queries' wrappers share: KBHIP_EINVAL with "<call><what>"
+namespace kbhip {
+inline void refuse_unless(bool ok, const char* call, const char* what) {
+    if (!ok) throw Error(KBHIP_EINVAL, string(call) + what);
+}
+inline void check_cap(const char* call, int cap) { refuse_unless(cap >= 1 && cap <= 64, call, ": cap is 1 .. 64"); }
+inline void check_by_score(const char* call, int v) { refuse_unless(v == 0 || v == 1, call, ": by_score is 0 or 1"); }
+inline void check_stride(const char* call, int v) { refuse_unless(v >= 1, call, ": stride is at least 1"); }
+inline void check_cap_ops(const char* call, int64_t v) { refuse_unless(v >= 1, call, ": cap_ops is at least 1"); }
+inline void check_victims(const char* call, int v, bool or_none = false) {  // or_none: 0 passes (kbhip_rank_heads)
+    refuse_unless(v >= (or_none ? 0 : KBHIP_VICTIMS_OTHER_QUEUES) && v <= KBHIP_VICTIMS_SAME_JOB, call,
+                  or_none ? ": victims is 0 or one of KBHIP_VICTIMS_* (1..3)" : ": victims is one of KBHIP_VICTIMS_* (1..3)");
+}
+}  // namespace kbhip
 
 #define ABI_GUARD(...)                                       \
     try {                                                    \

@@ -27,22 +27,28 @@ HEADS_VICTIMS_MAX = 64  # KBHIP_HEADS_VICTIMS_MAX: tasks per kbhip_heads_victims
 HEAD_VICTIMS_VALID, HEAD_VICTIMS_COVERS = 1, 2  # kbhip_head_victims: out_flags bits
 WALK_ASSIGNED, WALK_EXHAUSTED, WALK_HEAD_END, WALK_CAPACITY = 1, 2, 3, 4  # kbhip_walk_victims: stop reasons
 _WALK_INFO = ("stop", "total", "visited", "acted", "last_node", "last_score", "launches")
-
-
-def _walk_info(info):
-    d = dict(zip(_WALK_INFO, map(int, info[:7])))
-    d.update(rebuilt=int(info[7]) & 1, state_rebuilt=(int(info[7]) >> 1) & 1, patched=int(info[7]) >> 8)
-    return d
-
-
 _WALK_FROM_INFO = ("stop", "remaining", "visited", "acted", "resume_node", "resume_score", "launches")
 
 
-def _walk_from_info(info):
-    d = dict(zip(_WALK_FROM_INFO, map(int, info[:7])))
-    d.update(rebuilt=int(info[7]) & 1, state_rebuilt=(int(info[7]) >> 1) & 1, patched=int(info[7]) >> 8,
-             last_node=int(info[8]), first_valid=int(info[9]))
+def _walk_info(info, names=_WALK_INFO, tail=()):
+    """out_info of either walk: seven named words, the packed word 7, then the words named by `tail`."""
+    d = dict(zip(names, map(int, info[:7])))
+    d.update(rebuilt=int(info[7]) & 1, state_rebuilt=(int(info[7]) >> 1) & 1, patched=int(info[7]) >> 8)
+    d.update(zip(tail, map(int, info[8:])))
     return d
+
+
+def _walk_from_info(info):
+    return _walk_info(info, _WALK_FROM_INFO, ("last_node", "first_valid"))
+
+
+def _walk_arrays(cap_ops, info_words=8):
+    """(op, pod, node, info) for a walk call of up to cap_ops ops"""
+    room = max(int(cap_ops), 1)
+    return (np.zeros(room, np.uint8), np.full(room, -1, np.int32), np.full(room, -1, np.int32),
+            np.zeros(info_words, np.int64))
+
+
 # kbhip_explain_tasks: the verdict codes (low four bits of a verdict byte), the short bits of codes 0..2
 (WHY_FITS_IDLE, WHY_FITS_RELEASING, WHY_RESOURCES, WHY_POD_COUNT, WHY_NODE_SELECTOR, WHY_HOST_PORTS,
  WHY_UNSCHEDULABLE, WHY_TAINTS, WHY_POD_AFFINITY, WHY_SCORE_ERROR) = range(10)
@@ -350,6 +356,20 @@ class Session:
         return (total[:n].copy(), node[: n * cap].reshape(shape), score[: n * cap].reshape(shape),
                 cands[: n * cap].reshape(shape), info)
 
+    @staticmethod
+    def _head_arrays(rows: int, stride: int):
+        """(node, score, count, evict, flags, victim) of head_victims / heads_victims for `rows` head entries"""
+        return (np.full(rows, -1, np.int32), np.zeros(rows, np.int32), np.zeros(rows, np.int32),
+                np.zeros(rows, np.int32), np.zeros(rows, np.uint8), np.full(rows * max(stride, 1), -1, np.int32))
+
+    def _walk(self, fn, info_words, decode, task_id, by_score, victims, cap, after, cap_ops):  # either walk call
+        op, pod, node, info = _walk_arrays(cap_ops, info_words)
+        a_node, a_score = (-1, 0) if after is None else (int(after[0]), int(after[1]))
+        n = int(fn(self._h, int(task_id), int(by_score), int(victims), int(cap), a_node, a_score, _p(op), _p(pod),
+                   _p(node), int(cap_ops), _p(info)))
+        _check(n if n < 0 else 0)
+        return op[:n].copy(), pod[:n].copy(), node[:n].copy(), decode(info)
+
     def head_victims(self, task_id: int, by_score: bool = True, victims: int = VICTIMS_OTHER_QUEUES,
                      cap: int = 64, stride: int = 16):
         """kbhip_head_victims: the head of rank_victim_nodes' walk and, per head
@@ -360,13 +380,7 @@ class Session:
         stride) victims' pod indices, then -1.
         info: {"rebuilt", "state_rebuilt", "patched", "launches", "max_count"}."""
         cap, stride = int(cap), int(stride)
-        rows = max(cap, 1)
-        node = np.full(rows, -1, np.int32)
-        score = np.zeros(rows, np.int32)
-        count = np.zeros(rows, np.int32)
-        evict = np.zeros(rows, np.int32)
-        flags = np.zeros(rows, np.uint8)
-        victim = np.full(rows * max(stride, 1), -1, np.int32)
+        node, score, count, evict, flags, victim = self._head_arrays(max(cap, 1), stride)
         info = np.zeros(5, np.int64)
         n = int(lib().kbhip_head_victims(self._h, int(task_id), int(by_score), int(victims), cap, stride, _p(node),
                                          _p(score), _p(count), _p(evict), _p(flags), _p(victim), _p(info)))
@@ -388,14 +402,8 @@ class Session:
         "victim_launches"}."""
         ids = np.ascontiguousarray(task_ids, dtype=np.int32).reshape(-1)
         n, cap, stride = int(ids.size), int(cap), int(stride)
-        rows = max(n, 1) * max(cap, 1)
         total = np.zeros(max(n, 1), np.int64)
-        node = np.full(rows, -1, np.int32)
-        score = np.zeros(rows, np.int32)
-        count = np.zeros(rows, np.int32)
-        evict = np.zeros(rows, np.int32)
-        flags = np.zeros(rows, np.uint8)
-        victim = np.full(rows * max(stride, 1), -1, np.int32)
+        node, score, count, evict, flags, victim = self._head_arrays(max(n, 1) * max(cap, 1), stride)
         first = np.full(max(n, 1), -1, np.int32)
         info = np.zeros(6, np.int64)
         r = int(lib().kbhip_heads_victims(self._h, _p(ids), n, int(by_score), int(victims), cap, stride, _p(total),
@@ -419,15 +427,7 @@ class Session:
         info: {"stop" (a WALK_* reason), "total", "visited", "acted",
         "last_node", "last_score", "launches", "rebuilt", "state_rebuilt",
         "patched"}."""
-        cap_ops = int(cap_ops)
-        room = max(cap_ops, 1)
-        op, pod, node = np.zeros(room, np.uint8), np.full(room, -1, np.int32), np.full(room, -1, np.int32)
-        info = np.zeros(8, np.int64)
-        a_node, a_score = (-1, 0) if after is None else (int(after[0]), int(after[1]))
-        n = int(lib().kbhip_walk_victims(self._h, int(task_id), int(by_score), int(victims), int(cap), a_node, a_score,
-                                         _p(op), _p(pod), _p(node), cap_ops, _p(info)))
-        _check(n if n < 0 else 0)
-        return op[:n].copy(), pod[:n].copy(), node[:n].copy(), _walk_info(info)
+        return self._walk(lib().kbhip_walk_victims, 8, _walk_info, task_id, by_score, victims, cap, after, cap_ops)
 
     def walk_victims_from(self, task_id: int, by_score: bool = True, victims: int = VICTIMS_OTHER_QUEUES,
                           cap: int = 64, after=None, cap_ops: int = 4096):
@@ -440,15 +440,8 @@ class Session:
         resume point at the call), "visited", "acted", "resume_node",
         "resume_score", "launches", "rebuilt", "state_rebuilt", "patched",
         "last_node", "first_valid"}."""
-        cap_ops = int(cap_ops)
-        room = max(cap_ops, 1)
-        op, pod, node = np.zeros(room, np.uint8), np.full(room, -1, np.int32), np.full(room, -1, np.int32)
-        info = np.zeros(10, np.int64)
-        a_node, a_score = (-1, 0) if after is None else (int(after[0]), int(after[1]))
-        n = int(lib().kbhip_walk_victims_from(self._h, int(task_id), int(by_score), int(victims), int(cap), a_node,
-                                              a_score, _p(op), _p(pod), _p(node), cap_ops, _p(info)))
-        _check(n if n < 0 else 0)
-        return op[:n].copy(), pod[:n].copy(), node[:n].copy(), _walk_from_info(info)
+        return self._walk(lib().kbhip_walk_victims_from, 10, _walk_from_info, task_id, by_score, victims, cap, after,
+                          cap_ops)
 
     def explain_tasks(self, task_ids, verdicts: bool = False, n_nodes: Optional[int] = None):
         """kbhip_explain_tasks: why each node is, or is not, in the allocate
@@ -748,12 +741,9 @@ class EncodedSnapshot:
         in the given order, by the kernel's own functions on the host tables:
         (ops[n], pods[n], nodes[n], info) as Session.walk_victims."""
         nd = np.ascontiguousarray(nodes, dtype=np.int32).reshape(-1)
-        cap_ops = int(cap_ops)
-        room = max(cap_ops, 1)
-        op, pod, node = np.zeros(room, np.uint8), np.full(room, -1, np.int32), np.full(room, -1, np.int32)
-        info = np.zeros(8, np.int64)
+        op, pod, node, info = _walk_arrays(cap_ops)
         n = int(lib().kbhip_debug_walk_victims(self._h, int(task_id), int(victims), _p(nd) if nd.size else None,
-                                               int(nd.size), cap_ops, _p(op), _p(pod), _p(node), _p(info)))
+                                               int(nd.size), int(cap_ops), _p(op), _p(pod), _p(node), _p(info)))
         _check(n if n < 0 else 0)
         return op[:n].copy(), pod[:n].copy(), node[:n].copy(), _walk_info(info)
 
