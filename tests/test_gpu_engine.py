@@ -6,7 +6,16 @@ gang close messages must equal the CPU oracle's and the launched kernels'
 with several nodes per thread, pops whose candidates were left out or dropped
 (the previous two pops'), a task that finds no node (the FitDelta histogram
 from the group count words), runs interleaved with launched pops (classes the
-engine does not serve), and a run that ends idle and is restarted."""
+engine does not serve), and a run that ends idle and is restarted.
+
+These are whole sessions on random and generator clusters.  The engine's own
+structure at its edges (worker, group and owner-segment seams, lists cut
+inside a tie, engine_groups, pops on the nodes the last four pops changed,
+127 / 128 score levels, the owners' backlog and class limits, run lengths
+around the restart hysteresis, sessions of 8 / 9 / 16 / 17 pops) is in
+tests/test_gpu_engine_edges.py, on the hand-placed clusters of
+tests/engineedges.py, whose claims tests/test_engine_edges.py checks on the
+restatements without a GPU."""
 import time
 
 import numpy as np
