@@ -588,6 +588,99 @@ func (e *Engine) WalkVictimsFrom(task int32, byScore bool, victims int32, cap in
 	return ops[:n], pods[:n], nodes[:n], info, nil
 }
 
+// WalkBeginInfo says what a WalkBegin call did (out_info of kbhip_walk_begin).
+type WalkBeginInfo struct {
+	Launches        int64
+	Rebuilt         bool  // the candidate table was built by this call
+	Bytes           int64 // device bytes the cursor keeps
+	AffinityTargets bool  // the task's class has predicates that read pod-affinity targets: with byScore false WalkVictimsFrom is the closer call
+}
+
+// WalkBegin ranks the task's pruned walk once and keeps it on the device as
+// the session's eviction-walk cursor (kbhip_walk_begin), replacing an earlier
+// one.  Returns the walk's total.
+func (e *Engine) WalkBegin(task int32, byScore bool, victims int32) (total int64, info WalkBeginInfo, err error) {
+	var raw [4]C.int64_t
+	n := C.kbhip_walk_begin(e.s, C.int32_t(task), boolI32(byScore), C.int32_t(victims), &raw[0])
+	if n < 0 {
+		return 0, info, lastErr("walk_begin", C.int(n))
+	}
+	info = WalkBeginInfo{Launches: int64(raw[0]), Rebuilt: raw[1] != 0, Bytes: int64(raw[2]), AffinityTargets: raw[3] != 0}
+	return int64(n), info, nil
+}
+
+// WalkNextInfo says how a WalkNext call ended and what it did (out_info of
+// kbhip_walk_next).
+type WalkNextInfo struct {
+	Stop         int   // a Walk* reason: WalkExhausted = the end of the kept order was reached, WalkHeadEnd = cap serial entries are used up and entries remain
+	Total        int64 // entries of the kept order
+	Decided      int64 // entries passed over and visited
+	Acted        int64 // nodes evicted from
+	Next         int64 // the position the next call goes on from
+	First        int64 // the first position that could act against the session as it stands, -1 if none
+	Launches     int64
+	Rebuilt      bool  // the candidate table was built by this call
+	StateRebuilt bool  // the victim state was built by this call
+	Patched      int64 // records of earlier ApplyOps batches patched into it
+	LastNode     int32 // the last acted-on node, -1 if none
+	Scanned      int64 // entries the side-by-side scan decided
+}
+
+// WalkNext runs the cursor's walk from position pos of the kept order
+// (kbhip_walk_next): the entries that cannot act are passed over in one
+// launch, the serial walk covers up to cap entries from the first that can.
+// ops / pods / nodes go to ApplyOps unchanged; after a WalkHeadEnd or
+// WalkCapacity stop apply the ops and call again with Next.  1 <= cap <= 64,
+// capOps >= 1.
+func (e *Engine) WalkNext(pos int64, cap int, capOps int) (ops []uint8, pods, nodes []int32, info WalkNextInfo, err error) {
+	if cap < 1 || cap > 64 || capOps < 1 { // (also keeps &x[0] below off empty slices)
+		return nil, nil, nil, info, fmt.Errorf("kbhip walk_next: cap %d (1..64), capOps %d (>= 1)", cap, capOps)
+	}
+	ops, pods, nodes = make([]uint8, capOps), make([]int32, capOps), make([]int32, capOps)
+	var raw [10]C.int64_t
+	n := C.kbhip_walk_next(e.s, C.int64_t(pos), C.int32_t(cap), (*C.uint8_t)(unsafe.Pointer(&ops[0])),
+		(*C.int32_t)(unsafe.Pointer(&pods[0])), (*C.int32_t)(unsafe.Pointer(&nodes[0])), C.int64_t(capOps), &raw[0])
+	if n < 0 {
+		return nil, nil, nil, info, lastErr("walk_next", C.int(n))
+	}
+	info = WalkNextInfo{Stop: int(raw[0]), Total: int64(raw[1]), Decided: int64(raw[2]), Acted: int64(raw[3]),
+		Next: int64(raw[4]), First: int64(raw[5]), Launches: int64(raw[6]), Rebuilt: raw[7]&1 != 0,
+		StateRebuilt: raw[7]&2 != 0, Patched: int64(raw[7]) >> 8, LastNode: int32(raw[8]), Scanned: int64(raw[9])}
+	return ops[:n], pods[:n], nodes[:n], info, nil
+}
+
+// WalkOrder copies entries [first, first+cap) of the cursor's kept order
+// (kbhip_walk_order): the nodes and, with byScore, their scores.  Returns the
+// walk's total.
+func (e *Engine) WalkOrder(first int64, cap int) (total int64, nodes, scores []int32, err error) {
+	if first < 0 || cap < 0 {
+		return 0, nil, nil, fmt.Errorf("kbhip walk_order: first %d, cap %d (>= 0)", first, cap)
+	}
+	nodes, scores = make([]int32, cap+1), make([]int32, cap+1) // (+1 keeps &x[0] off empty slices)
+	n := C.kbhip_walk_order(e.s, C.int64_t(first), (*C.int32_t)(unsafe.Pointer(&nodes[0])),
+		(*C.int32_t)(unsafe.Pointer(&scores[0])), C.int64_t(cap))
+	if n < 0 {
+		return 0, nil, nil, lastErr("walk_order", C.int(n))
+	}
+	k := int64(n) - first
+	if k < 0 {
+		k = 0
+	}
+	if k > int64(cap) {
+		k = int64(cap)
+	}
+	return int64(n), nodes[:k], scores[:k], nil
+}
+
+// WalkEnd drops the cursor (kbhip_walk_end); whether one was open.
+func (e *Engine) WalkEnd() (bool, error) {
+	r := C.kbhip_walk_end(e.s)
+	if r < 0 {
+		return false, lastErr("walk_end", r)
+	}
+	return r != 0, nil
+}
+
 // The verdict codes of ExplainTasks (KBHIP_WHY_*): the low four bits of a
 // verdict byte; the WhyShort* bits accompany the codes 0..2.
 const (

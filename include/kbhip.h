@@ -623,6 +623,92 @@ int64_t kbhip_walk_victims_from(kb_session* s, int32_t task_id, int32_t by_score
                                 uint8_t* out_op, int32_t* out_pod, int32_t* out_node, int64_t cap_ops,
                                 int64_t* out_info /* optional, 10 */);
 
+/* kbhip_walk_begin / kbhip_walk_next / kbhip_walk_order / kbhip_walk_end <- the
+ * same node loop over a walk that is ranked once and kept: the eviction-walk
+ * cursor.  A session holds one cursor; kbhip_walk_begin replaces it.
+ * kbhip_walk_begin ranks the task's pruned walk once — exactly the order and
+ * the victim test of kbhip_rank_victim_nodes(task, by_score, victims, ..) on its
+ * full-sort path, on the session as it stands — keeps the ranked keys in a
+ * device buffer of the cursor's own, which no other call writes, and returns the
+ * walk's total T.  out_info (optional, 4 entries): [0] kernel launches
+ * (kbhip_rank_victim_nodes' full-path count: the sort's, the compaction's three,
+ * and one when pod-affinity count changes were pending), [1] whether the
+ * candidate table was rebuilt, [2] the device bytes the cursor keeps, [3] 1 when
+ * the task's class has predicates that read pod-affinity targets (see "Order").
+ * KBHIP_EINVAL, KBHIP_EUNSUPPORTED and KBHIP_EDEVICE (a score outside the class
+ * range) as kbhip_rank_victim_nodes; a task without a job is refused too.  A
+ * call that fails before it overwrites the kept keys — every refusal, and
+ * KBHIP_EUNSUPPORTED — leaves an open cursor as it was; after a later failure
+ * none is open.
+ * kbhip_walk_next decides entries [pos, T) of the kept order in two launches.
+ * The scan decides every one of them side by side against the session as it
+ * stands (kbhip_head_victims' decision, nothing carried) and yields `first`: the
+ * lowest position whose decision is KBHIP_HEAD_VICTIMS_VALID.  The entries
+ * [pos, first) are passed over and counted: no eviction of this call precedes
+ * them, so that answer is the walk's.  From `first` the serial loop of
+ * kbhip_walk_victims runs over at most `cap` entries — the entry at `first`
+ * too is decided by it, and no entry behind it by the scan: carried evictions
+ * can turn a node that was not VALID into one that is.  cap_ops, the
+ * all-or-nothing steps, the carried state's capacities (option
+ * "walk_overlay_max"), "the first node a call acts on is taken" and the op
+ * format for kbhip_apply_ops are kbhip_walk_victims'.  (An entry whose node holds
+ * more candidate tasks than a block stages in LDS, 256, is not decided by the
+ * scan: it counts as `first`, and the serial loop decides it exactly and passes
+ * it over if it is not VALID.)
+ * Stop reasons: KBHIP_WALK_ASSIGNED and KBHIP_WALK_CAPACITY as there;
+ *   KBHIP_WALK_EXHAUSTED  position T was reached.
+ *   KBHIP_WALK_HEAD_END   `cap` serial entries are used up and entries remain.
+ * out_info (optional, 10 entries): [0] the stop reason, [1] T, [2] entries
+ * decided — passed over plus visited, a node refused with KBHIP_WALK_CAPACITY
+ * counted as kbhip_walk_victims counts it — [3] nodes acted on, [4] the next
+ * position: behind the last entry passed over or acted on (a node refused with
+ * KBHIP_WALK_CAPACITY is met again), [5] `first` (-1: none), [6] kernel launches
+ * (2, plus one when records were patched into the victim state and one when
+ * pod-affinity count changes were pending), [7] as kbhip_walk_victims' [7],
+ * [8] the last acted-on node (-1: none), [9] the entries the scan decided
+ * (informational: a block behind a `first` already found may leave undecided,
+ * so first - pos + 1 <= [9] <= T - pos when `first` exists).
+ * Returns the ops written; one copy back, one wait.
+ * Host protocol: kbhip_walk_begin; then kbhip_walk_next(pos = 0), kbhip_apply_ops,
+ * kbhip_walk_next(out_info[4]) .. until KBHIP_WALK_ASSIGNED or
+ * KBHIP_WALK_EXHAUSTED.  One ranking per task, and a task that can act on no
+ * node is settled by the second call.
+ * kbhip_walk_order copies entries [first, first + cap) of the kept order (the
+ * nodes; the scores with by_score 1, else 0) and returns T: what a host logs.
+ * kbhip_walk_end drops the cursor: 1, or 0 when none was open.
+ * Order.  With by_score 1 the kept order is the reference's for every task
+ * class: preempt.go:270-288 evaluates the predicates and the scores once,
+ * before the node loop.  With by_score 0 the reference tests the predicate at
+ * each node as its loop reaches it (reclaim.go:115-117), and the cursor fixed
+ * the node set at kbhip_walk_begin; the two differ only for task classes whose
+ * predicates read pod-affinity targets that an applied eviction removed.
+ * kbhip_walk_begin's out_info[3] names such a class, and for it
+ * kbhip_walk_victims_from stays the closer call.  Pruning is not affected: the
+ * evictions of this walk take candidates only off nodes in front of the next
+ * position, and a node that other evictions made prunable merely stays in the
+ * order and is decided not VALID.
+ * Lifetime.  The cursor survives a successful kbhip_apply_ops and every
+ * read-only call (the rankings, head, victims, explain and walk queries,
+ * kbhip_sweep_scores, stats, read-backs).  Every call that leaves the candidate
+ * table and the victim state stale drops it: the actions, kbhip_place_job and
+ * its asynchronous forms, kbhip_first_fit, the carry-overs, a kbhip_apply_ops
+ * that failed part way; so do kbhip_walk_end, kbhip_walk_begin and
+ * kbhip_session_close.
+ * Read-only as kbhip_walk_victims.  Each call is validated before any device
+ * work, and a refused call writes nothing.  KBHIP_EINVAL (kbhip_walk_next,
+ * kbhip_walk_order): no cursor open; kbhip_walk_next also: the cursor's task is
+ * no longer Pending (its own KBHIP_OP_PIPELINE was applied), pos outside 0 .. T,
+ * cap outside 1 .. 64, cap_ops < 1, a null out_op, out_pod or out_node, an
+ * encode-only session, submitted pops outstanding.  KBHIP_EUNSUPPORTED: a
+ * node-sharded session. */
+int64_t kbhip_walk_begin(kb_session* s, int32_t task_id, int32_t by_score, int32_t victims /* KBHIP_VICTIMS_* */,
+                         int64_t* out_info /* optional, 4 */);
+int64_t kbhip_walk_next(kb_session* s, int64_t pos, int32_t cap /* 1..64 serial entries */,
+                        uint8_t* out_op, int32_t* out_pod, int32_t* out_node, int64_t cap_ops,
+                        int64_t* out_info /* optional, 10 */);
+int64_t kbhip_walk_order(kb_session* s, int64_t first, int32_t* out_node, int32_t* out_score /* optional */, int64_t cap);
+int     kbhip_walk_end(kb_session* s);   /* 1: a cursor was dropped, 0: none was open */
+
 /* kbhip_explain_tasks <- why each node is, or is not, a node of the allocate
  * walk of up to KBHIP_EXPLAIN_MAX pending tasks, on the session as it stands:
  * what the reference logs node by node (allocate.go:128-137, the error

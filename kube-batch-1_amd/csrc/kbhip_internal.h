@@ -334,6 +334,22 @@ hipError_t launch_walk_victims_from(const VictState& st, const VictHdr& h, const
                                     int node_base, int lds_recs, VictRec* spill, int spill_stride, int ov_cap_j,
                                     int ov_cap_q, int64_t cap_ops, int32_t* flags, int64_t* out_info,
                                     int32_t* out_pod, int32_t* out_node, hipStream_t stm);
+// kbhip_walk_next (kbhip_victims.hip): the walk over entries [pos, total) of a kept order — `keys` is
+// launch_vict_compact's output, `total` its count — in two launches.  k_walk_scan: one wave per entry (a
+// bounded grid of one-wave blocks, each taking every grid-th entry until it meets one behind the result so
+// far), each decided against the state as it stands; scan[0] = the lowest position whose decision
+// is VALID (an atomicMin by lane 0; any value >= total: none), scan[1] = the entries it decided; both words
+// are as launch_walk_scan_init leaves them when the launch starts, and k_walk_cursor puts them back, so a
+// call that fails between the two launches ends the cursor.  An entry whose node holds more than lds_recs records is not
+// decided by the scan and counts as VALID for it.  k_walk_cursor: one block; the entries before scan[0] are
+// passed over, from it on the loop k_walk_victims runs over at most `cap` entries, with the one spill row.
+// out_info (10 int64): stop, total, entries decided (passed over and visited), acted, the next position,
+// scan[0]'s position (-1: none), ops, 0, the last acted-on node (-1), scan[1].
+hipError_t launch_walk_scan_init(uint32_t* scan, hipStream_t stm);
+hipError_t launch_walk_cursor(const VictState& st, const VictHdr& h, const uint64_t* keys, int64_t pos, int64_t total,
+                              int cap, int task, int node_base, int lds_recs, VictRec* spill, int spill_stride,
+                              int ov_cap_j, int ov_cap_q, int64_t cap_ops, uint32_t* scan, int64_t* out_info,
+                              int32_t* out_pod, int32_t* out_node, hipStream_t stm);
 
 // Selection-key format of a batched launch: 32-bit keys when the class's
 // score range and the node count fit (kbhip_kernels.hip, PopArgs).

@@ -37,8 +37,14 @@
 //                    the caller's resume point decided side by side (flags
 //                    only), then the same walk_loop from the first entry that
 //                    can act.
+//   k_walk_scan, k_walk_cursor
+//                    kbhip_walk_next: every entry of a kept order at or behind
+//                    a position decided side by side, one wave per entry, into one
+//                    word (the lowest position that can act), then walk_loop
+//                    from that position.
 //   k_victims_patch  the records kbhip_apply_ops left dirty, one thread each.
-// Stores are plain vector stores; nothing is atomic, no block waits for another.
+// Stores are plain vector stores; the only atomics are k_walk_scan's two (a vector atomicMin and a vector
+// atomicAdd per block, by lane 0); no block waits for another.
 #include <hip/hip_runtime.h>
 
 #include "kbhip_eval.h"
@@ -58,17 +64,14 @@ __device__ __forceinline__ bool head_node_range(const VictState& st, uint64_t ke
     return off >= 0 && n >= 0 && off + n <= st.n_tasks && (n <= lds_cap || (spill && n <= spill_stride));
 }
 
-// Head entry i of `head` (the keys, then the count) decided into `row` (count, evict, flags, then stride
-// victims), by one wave: what k_head_victims and k_heads_victims run per block.  lds: room for lds_cap
-// staged records; a longer node stages into spill_row (spill_stride records, or null).  An entry at or
-// beyond the head's count, or without a node, writes 0 / -1 and reads nothing of the state.
-__device__ __forceinline__ void head_victims_row(const VictState& st, const VictHdr& h, const uint64_t* head, int i,
-                                                 int stride, int node_base, VictRec* lds, int lds_cap,
-                                                 VictRec* spill_row, int spill_stride, int32_t* row) {
+// The node of `key` decided into `row` (count, evict, flags, then stride victims), by one wave.  lds: room
+// for lds_cap staged records; a longer node stages into spill_row (spill_stride records, or null).  in false,
+// or a key without a node: 0 / -1 written, nothing of the state read.
+__device__ __forceinline__ void victims_row(const VictState& st, const VictHdr& h, uint64_t key, bool in, int stride,
+                                            int node_base, VictRec* lds, int lds_cap, VictRec* spill_row,
+                                            int spill_stride, int32_t* row) {
     const int lane = threadIdx.x;
-    const uint64_t key = head[i], total = head[kTopK];
     int off = 0, n;
-    const bool in = ((uint64_t)i < total) & (key != 0);  // (&: the key's and the count's loads are in flight together)
     if (!in || !head_node_range(st, key, node_base, lds_cap, spill_row, spill_stride, off, n)) n = -1;  // no node
     int count = 0;
     if (n > 0) {  // (uniform over the block)
@@ -89,6 +92,17 @@ __device__ __forceinline__ void head_victims_row(const VictState& st, const Vict
         row[0] = row[1] = row[2] = 0;
     }
     for (int k = (count < stride ? count : stride) + lane; k < stride; k += 64) row[3 + k] = -1;
+}
+
+// Head entry i of `head` (the keys, then the count) decided into `row` by one wave: what k_head_victims and
+// k_heads_victims run per block.  An entry at or beyond the head's count, or without a node, writes 0 / -1
+// and reads nothing of the state.
+__device__ __forceinline__ void head_victims_row(const VictState& st, const VictHdr& h, const uint64_t* head, int i,
+                                                 int stride, int node_base, VictRec* lds, int lds_cap,
+                                                 VictRec* spill_row, int spill_stride, int32_t* row) {
+    const uint64_t key = head[i], total = head[kTopK];
+    const bool in = ((uint64_t)i < total) & (key != 0);  // (&: the key's and the count's loads are in flight together)
+    victims_row(st, h, key, in, stride, node_base, lds, lds_cap, spill_row, spill_stride, row);
 }
 
 __global__ __launch_bounds__(64) void k_head_victims(VictState st, VictHdr h, const uint64_t* head, int cap, int stride,
@@ -182,11 +196,13 @@ __device__ __forceinline__ void walk_entry(const VictState& st, WalkLds& s, cons
 }
 
 // Entries [i, lim) of `head` in order until one stops the walk, then out_info[0 .. 3] and [6]: the stop reason,
-// the head's count, the visits, the nodes acted on, the ops.  kHead (k_walk_victims): at most `cap` visits, and
-// an entry whose key is not below after_key (0: none) is left out.  (Every condition is uniform over the block.)
+// `total` (the count of the order `head` is part of: entries at and beyond it do not exist), the visits, the
+// nodes acted on, the ops.  kHead (k_walk_victims): at most `cap` visits, and an entry whose key is not below
+// after_key (0: none) is left out.  (Every condition is uniform over the block.)
 template <bool kHead>
 __device__ __forceinline__ void walk_loop(const VictState& st, WalkLds& s, const WalkArgs& a, const uint64_t* head,
-                                          int i, int lim, int cap, uint64_t after_key, int* res, int64_t* out_info) {
+                                          int i, int lim, int cap, uint64_t after_key, uint64_t total, int* res,
+                                          int64_t* out_info) {
     for (; i < lim; ++i) {
         if (kHead && s.c.visited >= cap) break;
         const uint64_t key = head[i];
@@ -195,7 +211,6 @@ __device__ __forceinline__ void walk_loop(const VictState& st, WalkLds& s, const
         if (s.c.stop != 0) break;
     }
     if (threadIdx.x != 0) return;
-    const uint64_t total = head[kTopK];
     out_info[0] = s.c.stop != 0 ? s.c.stop : (uint64_t)i < total ? kWalkHeadEnd : kWalkExhausted;
     out_info[1] = (int64_t)total;
     out_info[2] = s.c.visited;
@@ -220,7 +235,7 @@ __global__ __launch_bounds__(kWalkBlock) void k_walk_victims(VictState st, VictH
     const uint64_t total = head[kTopK];
     const int in_head = total < (uint64_t)kTopK ? (int)total : kTopK;
     walk_loop<true>(st, s, WalkArgs{node_base, spill, spill_stride, out_pod, out_node}, head, 0, in_head, cap,
-                    after_key, nullptr, out_info);
+                    after_key, total, nullptr, out_info);
     if (tid == 0) {
         out_info[4] = s.c.last_node;
         out_info[5] = s.c.last_score;
@@ -274,7 +289,7 @@ __global__ __launch_bounds__(kWalkBlock) void k_walk_victims_from(VictState st, 
     }
     __syncthreads();
     walk_loop<false>(st, s, WalkArgs{node_base, spill, spill_stride, out_pod, out_node}, head,
-                     s_first < 0 ? lim : s_first, lim, cap, 0, &s_res, out_info);
+                     s_first < 0 ? lim : s_first, lim, cap, 0, total, &s_res, out_info);
     if (tid == 0) {
         const int res = s_res;
         out_info[4] = res >= 0 ? key_idx(head[res]) : -1;
@@ -283,6 +298,112 @@ __global__ __launch_bounds__(kWalkBlock) void k_walk_victims_from(VictState st, 
         out_info[8] = s.c.last_node;
         out_info[9] = s_first;
     }
+}
+
+// kbhip_walk_next, the scan: entry i of the kept order `keys` (total entries), pos <= i < total, is decided
+// against the state as it stands by one wave — victims_row with no victim row, its three words in LDS — and
+// the lowest position whose decision is VALID is formed in scan[0] by lane 0's atomicMin (a vector atomic;
+// the word is ~0 when the launch starts — kbhip_walk_begin sets it, k_walk_cursor puts it back — so "none" is
+// any value >= total).  The grid is at
+// most kWalkScanBlocks one-wave blocks; block b takes entries pos + b, pos + b + grid, ..: the entries in
+// flight at any moment are a stretch of about one grid's length, so few entries behind the result are
+// decided in vain, and a short remainder takes a short grid.  scan[1] += the entries a block decided, once
+// per block.
+// The early exit: before each entry the block reads the word, and an entry behind its present value cannot
+// lower it — nor can any later entry of the block — so the block ends.  That is a hint and nothing rests on
+// it: the load is relaxed, may be stale and may be missed altogether; the word only ever falls, so an entry
+// left out was behind the final value too, and every entry at or before the final value is decided — the
+// atomicMin alone forms the result.  (One load by the wave, made uniform: the branch is taken by the whole
+// block or not at all, before any barrier.)
+// The spill rule: the scan has no spill rows (one per entry in flight would be grid x longest node records),
+// so an entry whose node holds more records than the lds_recs staged in LDS is not decided here — it reports
+// itself as if VALID, and k_walk_cursor's serial loop, which owns the one spill row, decides it exactly.
+constexpr int kWalkScanBlocks = 2048;
+__global__ __launch_bounds__(64) void k_walk_scan(VictState st, VictHdr h, const uint64_t* __restrict__ keys, int pos,
+                                                  int total, int node_base, int lds_recs, uint32_t* scan) {
+    __shared__ int32_t s_row[3];
+    const int lane = threadIdx.x;
+    if (pos < 0) return;
+    uint32_t decided = 0;
+    for (int64_t at = (int64_t)pos + blockIdx.x; at < total; at += gridDim.x) {
+        const int i = (int)at;
+        const uint32_t seen = __builtin_amdgcn_readfirstlane(
+            __hip_atomic_load(&scan[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
+        if (seen < (uint32_t)i) break;
+        const uint64_t key = keys[i];
+        int off = 0, n = 0;
+        const bool fits = head_node_range(st, key, node_base, lds_recs, nullptr, 0, off, n);
+        bool cand = !fits && n > lds_recs;  // a node of the state longer than the LDS rows: the serial loop's
+        if (!cand) {
+            victims_row(st, h, key, fits, 0, node_base, s_dyn_rec, lds_recs, nullptr, 0, s_row);
+            cand = lane == 0 && (s_row[2] & 1) != 0;  // (lane 0 wrote the words it reads)
+        }
+        decided += 1;
+        if (lane == 0 && cand) atomicMin(&scan[0], (uint32_t)i);
+        __syncthreads();  // (one wave: the next entry's staging follows lane 0's reads of this one's)
+    }
+    if (lane == 0 && decided) atomicAdd(&scan[1], decided);
+}
+
+// kbhip_walk_next, the walk: one block.  first = min(scan[0], total).  Entries [pos, first) are passed over
+// and counted: no eviction of this call precedes them, so the overlay is empty and the scan's stateless
+// answer is the walk's.  From `first` the loop k_walk_victims_from runs, over at most `cap` entries of the
+// kept order: that entry too is decided by walk_step, and no entry after it by a flag.  s_res: the position
+// of the last entry passed over or acted on (an entry refused with kWalkCapacity is met again by the next call).
+__global__ __launch_bounds__(kWalkBlock) void k_walk_cursor(VictState st, VictHdr h0, const uint64_t* keys, int pos,
+                                                            int total, int cap, uint32_t* scan, int task,
+                                                            int node_base, VictRec* spill, int spill_stride,
+                                                            int ov_cap_j, int ov_cap_q, int64_t cap_ops,
+                                                            int64_t* out_info, int32_t* out_pod, int32_t* out_node) {
+    __shared__ WalkLds s;
+    __shared__ int s_res;
+    const int tid = threadIdx.x;
+    const uint32_t seen = scan[0];
+    const int first = seen < (uint32_t)total ? ((int)seen < pos ? pos : (int)seen) : total;
+    const int lim = total - first < cap ? total : first + cap;
+    if (tid == 0) {
+        s_res = first - 1;
+        s.h = h0;
+        walk_ov_init(s.ov, ov_cap_j, ov_cap_q);
+        s.c = WalkCtl{0, cap_ops, 0, first - pos, 0, -1, 0, task};
+    }
+    __syncthreads();
+    walk_loop<false>(st, s, WalkArgs{node_base, spill, spill_stride, out_pod, out_node}, keys, first, lim, cap, 0,
+                     (uint64_t)total, &s_res, out_info);
+    if (tid == 0) {
+        out_info[4] = s_res + 1;
+        out_info[5] = first < total ? first : -1;
+        out_info[7] = 0;
+        out_info[8] = s.c.last_node;
+        out_info[9] = scan[1];
+        scan[0] = ~0u;  // the two words as the next call's scan expects them (every thread read scan[0] before
+        scan[1] = 0;    // the first barrier)
+    }
+}
+
+// The scan's two words as k_walk_scan expects them: ~0 and 0 (kbhip_walk_begin; k_walk_cursor restores them).
+hipError_t launch_walk_scan_init(uint32_t* scan, hipStream_t stm) {
+    const hipError_t e = hipMemsetAsync(scan, 0xff, sizeof(uint32_t), stm);
+    return e != hipSuccess ? e : hipMemsetAsync(scan + 1, 0, sizeof(uint32_t), stm);
+}
+
+hipError_t launch_walk_cursor(const VictState& st, const VictHdr& h, const uint64_t* keys, int64_t pos, int64_t total,
+                              int cap, int task, int node_base, int lds_recs, VictRec* spill, int spill_stride,
+                              int ov_cap_j, int ov_cap_q, int64_t cap_ops, uint32_t* scan, int64_t* out_info,
+                              int32_t* out_pod, int32_t* out_node, hipStream_t stm) {
+    if (cap < 1 || cap > kTopK || cap_ops < 1 || lds_recs < 1 || lds_recs > kVictLds || pos < 0 || pos > total ||
+        total > INT32_MAX || !keys || !scan)
+        return hipErrorInvalidValue;
+    // (an empty remainder still takes both launches: the call's launch count does not depend on its position)
+    const int64_t left = total - pos;
+    hipLaunchKernelGGL(k_walk_scan, dim3(left < 1 ? 1u : left < kWalkScanBlocks ? (unsigned)left : (unsigned)kWalkScanBlocks),
+                       dim3(64),
+                       (size_t)lds_recs * sizeof(VictRec), stm, st, h, keys, (int)pos, (int)total, node_base, lds_recs,
+                       scan);
+    hipLaunchKernelGGL(k_walk_cursor, dim3(1), dim3(kWalkBlock), 0, stm, st, h, keys, (int)pos, (int)total, cap,
+                       scan, task, node_base, spill, spill_stride, ov_cap_j, ov_cap_q, cap_ops,
+                       out_info, out_pod, out_node);
+    return hipGetLastError();
 }
 
 hipError_t launch_walk_victims_from(const VictState& st, const VictHdr& h, const uint64_t* head, int cap, int task,

@@ -66,6 +66,14 @@ void vict_check_size(const Session& S) {
                                             std::to_string(bytes >> 20) + " MB, above the 512 MB limit");
 }
 
+void vict_compact_buffers(Session& S) {
+    if (S.b_vict_keys.p) return;
+    const int N = S.nc.n;
+    S.b_vict_keys.alloc<uint64_t>(std::max(N, 1));
+    S.b_vict_cands.alloc<int32_t>(std::max(N, 1));
+    S.b_vict_blk.alloc<uint32_t>((size_t)vict_blocks(N) + 1);
+}
+
 bool vict_ensure(Session& S) {
     if (S.vict_live) return false;
     vict_build(S);
@@ -207,11 +215,7 @@ int64_t rank_victim_nodes_abi(Session& S, int pod, bool by_score, int mode, int6
         const uint64_t* d_keys = (const uint64_t*)S.b_rank_sorted.p;  // the order the window is read from
         uint64_t* const h_rank = S.h_rank.as<uint64_t>();
         if (mode != 0) {
-            if (!S.b_vict_keys.p) {
-                S.b_vict_keys.alloc<uint64_t>(std::max(N, 1));
-                S.b_vict_cands.alloc<int32_t>(std::max(N, 1));
-                S.b_vict_blk.alloc<uint32_t>((size_t)vict_blocks(N) + 1);
-            }
+            vict_compact_buffers(S);
             HIPCHK(launch_vict_compact(d_keys, (const uint32_t*)S.b_rank_cnt.p, N, v, (uint32_t*)S.b_vict_blk.p,
                                        (uint64_t*)S.b_vict_keys.p, (int32_t*)S.b_vict_cands.p, S.stream));
             launches += 3;

@@ -41,16 +41,24 @@ VictPrep vict_prepare(Session& S, int batch_rows) {
     return VictPrep{rebuilt, vs_rebuilt, patched, launches};
 }
 
-// What kbhip_head_victims, kbhip_walk_victims and kbhip_walk_victims_from do before their own kernel: the
-// plugins opened, the call's header, both tables made current and the head sweep and merge of
-// kbhip_rank_victim_nodes enqueued — b_rank_head holds the head in stream order (bound != 0: the head
-// among the nodes whose key is below it).
-HeadPrep head_prepare(Session& S, const HPod& p, bool by_score, int mode, uint64_t bound) {
+// What every victim query does before it ranks or walks: the plugins opened, the call's header, both tables
+// made current (kbhip_walk_next stops here: it walks a kept order).
+HeadPrep state_prepare(Session& S, const HPod& p, int mode) {
     Framework F(S);
     F.open_plugins();  // drf / proportion as OnSessionOpen leaves them (kbhip_apply_ops opens them the same way)
     const VictHdr h = make_hdr(S, p, mode);
     const VictPrep vp = vict_prepare(S, 0);
-    int64_t launches = vp.launches;
+    return HeadPrep{h, vp, vp.launches};
+}
+
+// What kbhip_head_victims, kbhip_walk_victims and kbhip_walk_victims_from do before their own kernel:
+// state_prepare, then the head sweep and merge of kbhip_rank_victim_nodes enqueued — b_rank_head holds the
+// head in stream order (bound != 0: the head among the nodes whose key is below it).
+HeadPrep head_prepare(Session& S, const HPod& p, bool by_score, int mode, uint64_t bound) {
+    const HeadPrep sp = state_prepare(S, p, mode);
+    const VictHdr& h = sp.h;
+    const VictPrep& vp = sp.vp;
+    int64_t launches = sp.launches;
     vector<int32_t> own_node;
     vector<int64_t> own_sum;
     const VictArgs v = vict_args(S, p, mode, own_node, own_sum);

@@ -19,16 +19,9 @@ uint64_t resume_key(const Session& S, const char* call, int after_node, int afte
     return after_node < 0 ? 0 : pack_key(by_score ? after_score : 0, after_node, 0);
 }
 
-// One walk's device output in b_vs_out: info (info_words int64) | pods[dcap] | nodes[dcap] | extra_bytes, not
-// copied back.  dcap: no walk writes more ops than the tasks of kTopK nodes (or of the state) and one pipeline.
-struct WalkOut {
-    int64_t dcap;
-    size_t info_bytes, out_bytes;
-    uint8_t* d;
-    int64_t* info() const { return (int64_t*)d; }
-    int32_t* pods() const { return (int32_t*)(d + info_bytes); }
-    int32_t* nodes() const { return pods() + dcap; }
-};
+}  // namespace
+
+// (session.h: what the walk calls share around their kernel)
 WalkOut walk_layout(Session& S, int64_t cap_ops, int info_words, size_t extra_bytes) {
     const int64_t most = std::min<int64_t>((int64_t)kTopK * S.vs_max_tasks, S.vs_tasks) + 1,
                   dcap = std::min(cap_ops, most);
@@ -39,8 +32,6 @@ WalkOut walk_layout(Session& S, int64_t cap_ops, int info_words, size_t extra_by
     return WalkOut{dcap, info_bytes, out_bytes, (uint8_t*)S.b_vs_out.p};
 }
 
-// One copy back, one wait, the ops unpacked (evictions, and the pipeline that ends an assigned walk) and
-// out_info[7].  Returns the kernel's info words in h_vs_out; *n: the ops.
 const int64_t* walk_finish(Session& S, const WalkOut& o, const HeadPrep& hp, uint8_t* out_op, int32_t* out_pod,
                            int32_t* out_node, int64_t* out_info, int64_t* n) {
     HIPCHK(hipMemcpyAsync(S.h_vs_out.p, o.d, o.out_bytes, hipMemcpyDeviceToHost, S.stream));
@@ -56,8 +47,6 @@ const int64_t* walk_finish(Session& S, const WalkOut& o, const HeadPrep& hp, uin
     S.stats.sweeps++;
     return info;
 }
-
-}  // namespace
 
 // One task's eviction walk over the head (kbhip_walk_victims): kbhip_head_victims' preparation, then
 // k_walk_victims on the merged keys — the node loop with the evictions of the earlier nodes carried in an

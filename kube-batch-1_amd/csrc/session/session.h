@@ -17,7 +17,8 @@
 // (kbhip_head_victims and the preparation the victim queries share),
 // 16_heads_victims (kbhip_heads_victims), 17_walk_victims (kbhip_walk_victims,
 // kbhip_walk_victims_from), 18_victim_state (the victim state they read: build,
-// upload, patch).  buffers.h holds DevBuf
+// upload, patch), 19_walk_cursor (kbhip_walk_begin / kbhip_walk_next: the walk
+// over an order ranked once and kept).  buffers.h holds DevBuf
 // and PinnedBuf, the holders of pooled device and pinned memory.  framework.h, which
 // the parts running actions include, is the C++ mirror of the Go framework they
 // share: the heaps, the ordering plugins, the status index, the statements.
@@ -637,6 +638,16 @@ struct Session {
     // kbhip_walk_victims: option "walk_overlay_max" (tests; 0 = the full overlay): the touched jobs and the
     // touched queues a walk carries at most
     int32_t walk_ov_max = 0;
+    // kbhip_walk_begin / kbhip_walk_next (19_walk_cursor.cpp): the session's one eviction-walk cursor.
+    // b_wc_keys: the task's pruned walk, ranked once — launch_vict_compact's keys, compacted straight into
+    // it (one key per node of the session: the count is known only afterwards) and overwritten by nothing
+    // but the next kbhip_walk_begin; b_wc_scan: k_walk_scan's two words.  wc_open is cleared wherever the
+    // candidate table and the victim state go stale (vict_stale): the order was ranked on statuses that call
+    // changes.  A successful kbhip_apply_ops keeps it — those are the walk's own evictions.
+    bool wc_open = false, wc_by_score = false;
+    int32_t wc_task = -1, wc_mode = 0;
+    int64_t wc_total = 0;
+    DevBuf b_wc_keys, b_wc_scan;
     // kbhip_heads_victims: option "victims_spill_max" (bytes; tests lower it): the most b_vs_spill holds for
     // one victims launch of a batch — a batch that needs more runs as consecutive request ranges
     int64_t vs_spill_max = (int64_t)256 << 20;
@@ -877,6 +888,7 @@ struct Session {
         if (ev_ops) { (void)hipEventDestroy(ev_ops); ev_ops = nullptr; }
         vict_live = false;
         vs_live = false;
+        wc_open = false;
         h_out = nullptr;
         if (cu_masked) {  // streams of option "cu_split" are this session's own
             for (int k = 1; k <= kMaxDep; ++k)
@@ -895,7 +907,7 @@ struct Session {
                           &b_rank_radix, &b_rank_head, &b_ops, &b_vict, &b_vict_own, &b_vict_blk, &b_vict_keys,
                           &b_vict_cands, &b_heads_in, &b_heads, &b_explain_in, &b_explain_part, &b_explain_out,
                           &b_explain_v, &b_vs_off, &b_vs_task, &b_vs_job, &b_vs_queue, &b_vs_spill, &b_vs_patch,
-                          &b_vs_out,
+                          &b_vs_out, &b_wc_keys, &b_wc_scan,
                           &b_shard_send, &b_shard_recv, &b_tab_idx, &b_sweep_cnt, &b_dd_max, &b_cmp_mask, &b_cmp_blk,
                           &b_cmp_node, &b_cmp_val})
             b->release();
@@ -1242,10 +1254,12 @@ const HPod& query_task(const Session& S, int pod, const string& prefix, bool nee
 void query_begin(Session& S, const char* api_name);
 // kbhip_rank_victim_nodes (12_rank.cpp).  vict_stale: the call that follows changes pod statuses outside
 // kbhip_apply_ops — the victim-candidate table is rebuilt by the next ranking that needs it.
-// The victim state of kbhip_head_victims (18_victim_state.cpp) goes stale with it, and its dirty lists end.
+// The victim state of kbhip_head_victims (18_victim_state.cpp) goes stale with it, and its dirty lists end;
+// the eviction-walk cursor (kbhip_walk_begin), ranked on the statuses that call changes, is dropped.
 inline void vict_stale(Session& S) {
     S.vict_live = false;
     S.vs_live = false;
+    S.wc_open = false;
     S.vs_dirty_pod.clear();
     S.vs_dirty_job.clear();
     S.vs_dirty_queue.clear();
@@ -1263,6 +1277,7 @@ int64_t rank_victim_nodes_abi(Session& S, int pod, bool by_score, int mode, int6
 // live (true: built now).  vict_own_list: job jb's candidates per node, distinct nodes ascending with four
 // sums each.  vict_count_host: vict_cand's count of node n on the host copy of the table.
 bool vict_ensure(Session& S);
+void vict_compact_buffers(Session& S);  // the full path's compaction buffers (b_vict_blk / _keys / _cands), once
 void vict_check_size(const Session& S);  // refuses a candidate table above its limit (KBHIP_EUNSUPPORTED)
 void vict_own_list(const Session& S, int jb, vector<int32_t>& node, vector<int64_t>& sum);
 int64_t vict_count_host(const Session& S, int mode, int q, const vector<int32_t>& own_node,
@@ -1380,10 +1395,34 @@ struct HeadPrep {
     int64_t launches;
 };
 HeadPrep head_prepare(Session& S, const HPod& p, bool by_score, int mode, uint64_t bound = 0);
+// head_prepare without the ranking (kbhip_walk_next walks a kept order): the plugins opened, the call's
+// header, vict_prepare (launches: its own).
+HeadPrep state_prepare(Session& S, const HPod& p, int mode);
+// What the walk calls (17_walk_victims.cpp, 19_walk_cursor.cpp) share around their kernel.  walk_layout: one
+// walk's device output in b_vs_out: info (info_words int64) | pods[dcap] | nodes[dcap] | extra_bytes, not
+// copied back.  dcap: no walk writes more ops than the tasks of kTopK nodes (or of the state) and one
+// pipeline.  walk_finish: one copy back, one wait, the ops unpacked (evictions, and the pipeline that ends
+// an assigned walk) and out_info[7]; returns the kernel's info words in h_vs_out; *n: the ops.
+struct WalkOut {
+    int64_t dcap;
+    size_t info_bytes, out_bytes;
+    uint8_t* d;
+    int64_t* info() const { return (int64_t*)d; }
+    int32_t* pods() const { return (int32_t*)(d + info_bytes); }
+    int32_t* nodes() const { return pods() + dcap; }
+};
+WalkOut walk_layout(Session& S, int64_t cap_ops, int info_words, size_t extra_bytes);
+const int64_t* walk_finish(Session& S, const WalkOut& o, const HeadPrep& hp, uint8_t* out_op, int32_t* out_pod,
+                           int32_t* out_node, int64_t* out_info, int64_t* n);
 // kbhip_walk_victims_from (17_walk_victims.cpp): one window of a task's eviction walk behind a resume point
 int64_t walk_victims_from_abi(Session& S, int pod, bool by_score, int mode, int cap, int after_node, int after_score,
                               uint8_t* out_op, int32_t* out_pod, int32_t* out_node, int64_t cap_ops,
                               int64_t* out_info);
+// kbhip_walk_begin / kbhip_walk_next / kbhip_walk_order / kbhip_walk_end (19_walk_cursor.cpp)
+int64_t walk_begin_abi(Session& S, int pod, bool by_score, int mode, int64_t* out_info);
+int64_t walk_next_abi(Session& S, int64_t pos, int cap, uint8_t* out_op, int32_t* out_pod, int32_t* out_node,
+                      int64_t cap_ops, int64_t* out_info);
+int64_t walk_order_abi(Session& S, int64_t first, int32_t* out_node, int32_t* out_score, int64_t cap);
 
 }  // namespace kbhip
 

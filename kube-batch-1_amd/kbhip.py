@@ -28,6 +28,7 @@ HEAD_VICTIMS_VALID, HEAD_VICTIMS_COVERS = 1, 2  # kbhip_head_victims: out_flags 
 WALK_ASSIGNED, WALK_EXHAUSTED, WALK_HEAD_END, WALK_CAPACITY = 1, 2, 3, 4  # kbhip_walk_victims: stop reasons
 _WALK_INFO = ("stop", "total", "visited", "acted", "last_node", "last_score", "launches")
 _WALK_FROM_INFO = ("stop", "remaining", "visited", "acted", "resume_node", "resume_score", "launches")
+_WALK_NEXT_INFO = ("stop", "total", "decided", "acted", "next", "first", "launches")
 
 
 def _walk_info(info, names=_WALK_INFO, tail=()):
@@ -40,6 +41,10 @@ def _walk_info(info, names=_WALK_INFO, tail=()):
 
 def _walk_from_info(info):
     return _walk_info(info, _WALK_FROM_INFO, ("last_node", "first_valid"))
+
+
+def _walk_next_info(info):
+    return _walk_info(info, _WALK_NEXT_INFO, ("last_node", "scanned"))
 
 
 def _walk_arrays(cap_ops, info_words=8):
@@ -68,7 +73,8 @@ EXPORTS = ("kbhip_device_count", "kbhip_session_open", "kbhip_session_open_file"
            "kbhip_session_carry_snapshot", "kbhip_walk_visits", "kbhip_fit_deltas", "kbhip_rank_nodes",
            "kbhip_apply_ops", "kbhip_rank_victim_nodes", "kbhip_rank_heads", "kbhip_explain_tasks",
            "kbhip_debug_explain", "kbhip_head_victims", "kbhip_debug_victims", "kbhip_walk_victims",
-           "kbhip_debug_walk_victims", "kbhip_heads_victims", "kbhip_walk_victims_from")
+           "kbhip_debug_walk_victims", "kbhip_heads_victims", "kbhip_walk_victims_from",
+           "kbhip_walk_begin", "kbhip_walk_next", "kbhip_walk_order", "kbhip_walk_end")
 
 RED_MAX_U64, RED_MIN_I64, RED_MAX_I64, RED_SUM_I64 = 0, 1, 2, 3
 ALLREDUCE_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint64), ctypes.c_int32,
@@ -188,6 +194,13 @@ def lib() -> ctypes.CDLL:
         L.kbhip_debug_walk_victims.restype = i64
         L.kbhip_walk_victims_from.argtypes = [vp, i32, i32, i32, i32, i32, i32, vp, vp, vp, i64, vp]
         L.kbhip_walk_victims_from.restype = i64
+        L.kbhip_walk_begin.argtypes = [vp, i32, i32, i32, vp]
+        L.kbhip_walk_begin.restype = i64
+        L.kbhip_walk_next.argtypes = [vp, i64, i32, vp, vp, vp, i64, vp]
+        L.kbhip_walk_next.restype = i64
+        L.kbhip_walk_order.argtypes = [vp, i64, vp, vp, i64]
+        L.kbhip_walk_order.restype = i64
+        L.kbhip_walk_end.argtypes = [vp]
         _lib = L
     return _lib
 
@@ -442,6 +455,47 @@ class Session:
         "last_node", "first_valid"}."""
         return self._walk(lib().kbhip_walk_victims_from, 10, _walk_from_info, task_id, by_score, victims, cap, after,
                           cap_ops)
+
+    def walk_begin(self, task_id: int, by_score: bool = True, victims: int = VICTIMS_OTHER_QUEUES):
+        """kbhip_walk_begin: the task's pruned walk ranked once and kept on
+        the device as the session's eviction-walk cursor: (total, info).
+        info: {"launches", "rebuilt", "bytes", "affinity_targets"}."""
+        info = np.zeros(4, np.int64)
+        n = int(lib().kbhip_walk_begin(self._h, int(task_id), int(by_score), int(victims), _p(info)))
+        _check(n if n < 0 else 0)
+        return n, dict(zip(("launches", "rebuilt", "bytes", "affinity_targets"), map(int, info)))
+
+    def walk_next(self, pos: int = 0, cap: int = 64, cap_ops: int = 4096):
+        """kbhip_walk_next: the cursor's walk from position `pos` of the kept
+        order — the entries that cannot act passed over side by side, the
+        serial walk over up to `cap` entries from the first that can: (ops[n],
+        pods[n], nodes[n], info), ready for apply_ops; go on from info["next"].
+        info: {"stop" (a WALK_* reason), "total", "decided", "acted", "next",
+        "first" (-1: none), "launches", "rebuilt", "state_rebuilt", "patched",
+        "last_node", "scanned"}."""
+        op, pod, node, info = _walk_arrays(cap_ops, 10)
+        n = int(lib().kbhip_walk_next(self._h, int(pos), int(cap), _p(op), _p(pod), _p(node), int(cap_ops), _p(info)))
+        _check(n if n < 0 else 0)
+        return op[:n].copy(), pod[:n].copy(), node[:n].copy(), _walk_next_info(info)
+
+    def walk_order(self, first: int = 0, cap: Optional[int] = None):
+        """kbhip_walk_order: entries [first, first + cap) of the cursor's kept
+        order: (total, nodes, scores).  cap=None: every entry from `first`."""
+        fn = lib().kbhip_walk_order
+        if cap is None:
+            n = int(fn(self._h, int(first), None, None, 0))
+            _check(n if n < 0 else 0)
+            cap = max(n - int(first), 0)
+        node = np.full(max(int(cap), 1), -1, np.int32)
+        score = np.zeros(max(int(cap), 1), np.int32)
+        n = int(fn(self._h, int(first), _p(node), _p(score), int(cap)))
+        _check(n if n < 0 else 0)
+        k = max(min(n, int(first) + int(cap)) - int(first), 0)
+        return n, node[:k].copy(), score[:k].copy()
+
+    def walk_end(self) -> bool:
+        """kbhip_walk_end: drops the cursor; whether one was open."""
+        return bool(_check(lib().kbhip_walk_end(self._h)))
 
     def explain_tasks(self, task_ids, verdicts: bool = False, n_nodes: Optional[int] = None):
         """kbhip_explain_tasks: why each node is, or is not, in the allocate
