@@ -609,6 +609,23 @@ func (e *Engine) WalkBegin(task int32, byScore bool, victims int32) (total int64
 	return int64(n), info, nil
 }
 
+// WalkBeginLive opens the cursor for reclaim's order (kbhip_walk_begin_live),
+// exact for every task class.  For a class whose predicates read pod-affinity
+// targets the cursor is live (live true): the kept order leaves that predicate
+// out, WalkNext tests it on the count tables as they stand and returns behind
+// the first node it acts on, so the host calls ApplyOps and WalkNext once per
+// acting node.  For any other class the call is WalkBegin(task, false, victims).
+// (Source only: no Go toolchain has compiled this declaration.)
+func (e *Engine) WalkBeginLive(task int32, victims int32) (total int64, info WalkBeginInfo, live bool, err error) {
+	var raw [4]C.int64_t
+	n := C.kbhip_walk_begin_live(e.s, C.int32_t(task), C.int32_t(victims), &raw[0])
+	if n < 0 {
+		return 0, info, false, lastErr("walk_begin_live", C.int(n))
+	}
+	info = WalkBeginInfo{Launches: int64(raw[0]), Rebuilt: raw[1] != 0, Bytes: int64(raw[2]), AffinityTargets: raw[3] != 0}
+	return int64(n), info, raw[3] == 2, nil
+}
+
 // WalkNextInfo says how a WalkNext call ended and what it did (out_info of
 // kbhip_walk_next).
 type WalkNextInfo struct {

@@ -682,8 +682,8 @@ int64_t kbhip_walk_victims_from(kb_session* s, int32_t task_id, int32_t by_score
  * each node as its loop reaches it (reclaim.go:115-117), and the cursor fixed
  * the node set at kbhip_walk_begin; the two differ only for task classes whose
  * predicates read pod-affinity targets that an applied eviction removed.
- * kbhip_walk_begin's out_info[3] names such a class, and for it
- * kbhip_walk_victims_from stays the closer call.  Pruning is not affected: the
+ * kbhip_walk_begin's out_info[3] names such a class, and for it (by_score 0)
+ * kbhip_walk_begin_live below is the exact call.  Pruning is not affected: the
  * evictions of this walk take candidates only off nodes in front of the next
  * position, and a node that other evictions made prunable merely stays in the
  * order and is decided not VALID.
@@ -708,6 +708,44 @@ int64_t kbhip_walk_next(kb_session* s, int64_t pos, int32_t cap /* 1..64 serial 
                         int64_t* out_info /* optional, 10 */);
 int64_t kbhip_walk_order(kb_session* s, int64_t first, int32_t* out_node, int32_t* out_score /* optional */, int64_t cap);
 int     kbhip_walk_end(kb_session* s);   /* 1: a cursor was dropped, 0: none was open */
+
+/* kbhip_walk_begin_live <- the cursor opened for reclaim's loop (by_score 0) so
+ * that it is exact for every task class: reclaim.go:115-117 tests PredicateFn at
+ * each node as the loop reaches it, after the evictions of the nodes before.
+ * A class whose predicates read no pod-affinity targets: the call is
+ * kbhip_walk_begin(task, 0, victims, ..) in every respect — the kept order,
+ * out_info, and what kbhip_walk_next does.
+ * A class whose predicates read pod-affinity targets: the cursor is live.  The
+ * kept order holds, node index ascending and in by_score 0's key format, every
+ * node that passes the class's predicates with the pod-affinity predicate left
+ * out (static predicates, pod count and host ports as the by_score 0 ranking
+ * tests them) and kbhip_rank_victim_nodes' victim-candidate test; T is that
+ * count, at least kbhip_walk_begin's.  No sort runs: out_info[0] counts the
+ * launches made (the marks, the compaction's three, one for pending
+ * pod-affinity count changes), [1] and [2] as kbhip_walk_begin, [3] is 2.
+ * On a live cursor kbhip_walk_next tests the pod-affinity predicate itself, on
+ * the count tables as they stand when the call starts (every applied eviction
+ * included):
+ *   - an entry is VALID only where the predicate holds for its node and the
+ *     victims decision is VALID: the scan forms `first` by that rule.  A node of
+ *     more than 256 candidate tasks still counts as `first` undecided, the
+ *     predicate included.
+ *   - the serial loop tests the predicate before it stages an entry; an entry
+ *     that fails is passed over, counted in [2] and gives no op.
+ *   - the call ends behind the first node it acts on, so [3] is 0 or 1: its
+ *     evictions change the predicate's count tables only through
+ *     kbhip_apply_ops, and the next call reads them.  The stop reason is then
+ *     KBHIP_WALK_ASSIGNED when that node covers, else KBHIP_WALK_HEAD_END while
+ *     entries remain and KBHIP_WALK_EXHAUSTED at T (KBHIP_WALK_CAPACITY where
+ *     that first step could not be carried, as for every walk call).  A call
+ *     that acts on nothing stops as on any cursor.
+ * out_info keeps its ten meanings ([4] the next position).  The host protocol is
+ * the cursor's; it pays one call per node acted on.  kbhip_walk_order,
+ * kbhip_walk_end, the lifetime rules, the refusals (a failure before the kept
+ * keys are overwritten leaves an open cursor as it was) and KBHIP_EUNSUPPORTED
+ * on a node-sharded session are kbhip_walk_begin's. */
+int64_t kbhip_walk_begin_live(kb_session* s, int32_t task_id, int32_t victims /* KBHIP_VICTIMS_* */,
+                              int64_t* out_info /* optional, 4 */);
 
 /* kbhip_explain_tasks <- why each node is, or is not, a node of the allocate
  * walk of up to KBHIP_EXPLAIN_MAX pending tasks, on the session as it stands:

@@ -404,4 +404,31 @@ hipError_t launch_vict_compact(const uint64_t* sorted, const uint32_t* count, in
     return hipGetLastError();
 }
 
+// ---------------------------------------------------------------------------
+// The marks of kbhip_walk_begin_live: reclaim's order is the node index, so a
+// ranking without the pod-affinity predicate needs no sort — one node per
+// thread, keys[n] = eval_first_fit's key on a class whose affinity program is
+// off (the static predicates, pod count and host ports; 0 where one fails),
+// and the compaction above reads the array as a sorted ranking of nc.n keys
+// (vict_key_keep drops the zeros).  Plain stores; no counter is accumulated.
+// ---------------------------------------------------------------------------
+__global__ __launch_bounds__(kBlock) void k_live_keys(Conf cf, NodeCols nc, DevTables t, TaskClass c, uint64_t* keys,
+                                                      uint32_t* count) {
+    const int n = blockIdx.x * kBlock + threadIdx.x;
+    if (n < nc.n) keys[n] = eval_first_fit(cf, c, t, nc, n);
+    if (n == 0) {
+        count[0] = (uint32_t)(nc.n > 0 ? nc.n : 0);
+        count[1] = 0;
+    }
+}
+
+hipError_t launch_live_keys(const Conf& cf, const NodeCols& nc, const DevTables& t, const TaskClass& c, uint64_t* keys,
+                            uint32_t* count, hipStream_t st) {
+    if (!keys || !count) return hipErrorInvalidValue;
+    TaskClass plain = c;
+    plain.aff = 0;  // eval_first_fit leaves aff_pred out
+    hipLaunchKernelGGL(k_live_keys, dim3(vict_blocks(nc.n)), dim3(kBlock), 0, st, cf, nc, t, plain, keys, count);
+    return hipGetLastError();
+}
+
 }  // namespace kbhip

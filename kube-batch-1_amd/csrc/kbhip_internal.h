@@ -167,6 +167,12 @@ hipError_t launch_explain(const Conf& cf, const NodeCols& nc, const DevTables& t
 int vict_blocks(int n_nodes);
 hipError_t launch_vict_compact(const uint64_t* sorted, const uint32_t* count, int n_nodes, const VictArgs& v,
                                uint32_t* blk, uint64_t* out_keys, int32_t* out_cands, hipStream_t st);
+// kbhip_walk_begin_live's marks (kbhip_heads.hip): keys[n] = the by_score 0 key of node n where it passes
+// class c's predicates with the pod-affinity predicate left out (eval_first_fit on c with its affinity
+// program switched off), else 0, for every node; count[0] = the nodes, count[1] = 0.  The node order is the
+// walk order, so launch_vict_compact takes keys / count as it takes a sorted ranking's.  One launch.
+hipError_t launch_live_keys(const Conf& cf, const NodeCols& nc, const DevTables& t, const TaskClass& c, uint64_t* keys,
+                            uint32_t* count, hipStream_t st);
 // One session's ranking request in a batched launch (what-if sessions).
 struct RankDesc {
     Conf cf;
@@ -345,11 +351,24 @@ hipError_t launch_walk_victims_from(const VictState& st, const VictHdr& h, const
 // passed over, from it on the loop k_walk_victims runs over at most `cap` entries, with the one spill row.
 // out_info (10 int64): stop, total, entries decided (passed over and visited), acted, the next position,
 // scan[0]'s position (-1: none), ops, 0, the last acted-on node (-1), scan[1].
+// live (kbhip_walk_begin_live's cursor; null: kbhip_walk_begin's): `keys` left the class's pod-affinity
+// predicate out, and both kernels (their live instantiations) test it per entry on the count tables as they
+// stand — the scan before it stages an entry (a node longer than lds_recs is not decided in this either), the
+// walk before walk_entry; an entry that fails is counted as decided and gives no op.  The walk then ends
+// behind the first node it acts on: HEAD_END while entries remain, EXHAUSTED at total, ASSIGNED / CAPACITY as
+// walk_step sets them.
+struct WalkLive {
+    static constexpr bool kLive = true;
+    Conf cf;
+    NodeCols nc;
+    DevTables t;
+    TaskClass c;
+};
 hipError_t launch_walk_scan_init(uint32_t* scan, hipStream_t stm);
 hipError_t launch_walk_cursor(const VictState& st, const VictHdr& h, const uint64_t* keys, int64_t pos, int64_t total,
                               int cap, int task, int node_base, int lds_recs, VictRec* spill, int spill_stride,
                               int ov_cap_j, int ov_cap_q, int64_t cap_ops, uint32_t* scan, int64_t* out_info,
-                              int32_t* out_pod, int32_t* out_node, hipStream_t stm);
+                              int32_t* out_pod, int32_t* out_node, hipStream_t stm, const WalkLive* live = nullptr);
 
 // Selection-key format of a batched launch: 32-bit keys when the class's
 // score range and the node count fit (kbhip_kernels.hip, PopArgs).

@@ -42,6 +42,11 @@
 //                    a position decided side by side, one wave per entry, into one
 //                    word (the lowest position that can act), then walk_loop
 //                    from that position.
+//   k_walk_scan_live, k_walk_cursor_live
+//                    the same two for a cursor of kbhip_walk_begin_live, whose
+//                    kept order left the pod-affinity predicate out: both test
+//                    it per entry on the count tables as they stand, and the
+//                    walk ends behind the first node it acts on.
 //   k_victims_patch  the records kbhip_apply_ops left dirty, one thread each.
 // Stores are plain vector stores; the only atomics are k_walk_scan's two (a vector atomicMin and a vector
 // atomicAdd per block, by lane 0); no block waits for another.
@@ -318,9 +323,27 @@ __global__ __launch_bounds__(kWalkBlock) void k_walk_victims_from(VictState st, 
 // The spill rule: the scan has no spill rows (one per entry in flight would be grid x longest node records),
 // so an entry whose node holds more records than the lds_recs staged in LDS is not decided here — it reports
 // itself as if VALID, and k_walk_cursor's serial loop, which owns the one spill row, decides it exactly.
+// The live cursor (kbhip_walk_begin_live; L = WalkLive, else WalkFixed and nothing of this is compiled):
+// the kept order holds every node that passes the class's other predicates, and an entry is VALID only where
+// walk_live_pred — eval_first_fit's pod-affinity test, on the count tables as they stand — holds for its node
+// too.  The test comes before the staging: a few loads, the same for every lane (made uniform: the branch is
+// taken by the whole block or not at all, before any barrier), and an entry that fails stages nothing and
+// counts as decided.  The spill rule comes before the test: a node longer than the LDS rows reports itself
+// undecided, predicate included.  The early exit and the atomicMin's argument are untouched: an entry that
+// fails the predicate lowers nothing, as an entry that is not VALID.
+struct WalkFixed { static constexpr bool kLive = false; };
+__device__ __forceinline__ bool walk_live_pred(const WalkFixed&, uint64_t) { return true; }
+__device__ __forceinline__ bool walk_live_pred(const WalkLive& lv, uint64_t key) {
+    const int n = key_idx(key) - lv.nc.base;
+    if (key == 0 || n < 0 || n >= lv.nc.n) return true;  // no node of the session: what head_node_range makes of it
+    const bool ok = !(lv.cf.pred_on && lv.c.aff) || aff_pred(lv.c, lv.t, lv.nc, n);
+    return __builtin_amdgcn_readfirstlane((int)ok) != 0;
+}
 constexpr int kWalkScanBlocks = 2048;
-__global__ __launch_bounds__(64) void k_walk_scan(VictState st, VictHdr h, const uint64_t* __restrict__ keys, int pos,
-                                                  int total, int node_base, int lds_recs, uint32_t* scan) {
+template <class L>
+__device__ __forceinline__ void walk_scan(const VictState& st, const VictHdr& h, const uint64_t* __restrict__ keys,
+                                          int pos, int total, int node_base, int lds_recs, uint32_t* scan,
+                                          const L& lv) {
     __shared__ int32_t s_row[3];
     const int lane = threadIdx.x;
     if (pos < 0) return;
@@ -334,6 +357,12 @@ __global__ __launch_bounds__(64) void k_walk_scan(VictState st, VictHdr h, const
         int off = 0, n = 0;
         const bool fits = head_node_range(st, key, node_base, lds_recs, nullptr, 0, off, n);
         bool cand = !fits && n > lds_recs;  // a node of the state longer than the LDS rows: the serial loop's
+        if constexpr (L::kLive) {
+            if (!cand && !walk_live_pred(lv, key)) {  // (uniform) decided: it cannot act, and nothing was staged
+                decided += 1;
+                continue;
+            }
+        }
         if (!cand) {
             victims_row(st, h, key, fits, 0, node_base, s_dyn_rec, lds_recs, nullptr, 0, s_row);
             cand = lane == 0 && (s_row[2] & 1) != 0;  // (lane 0 wrote the words it reads)
@@ -344,17 +373,56 @@ __global__ __launch_bounds__(64) void k_walk_scan(VictState st, VictHdr h, const
     }
     if (lane == 0 && decided) atomicAdd(&scan[1], decided);
 }
+__global__ __launch_bounds__(64) void k_walk_scan(VictState st, VictHdr h, const uint64_t* __restrict__ keys, int pos,
+                                                  int total, int node_base, int lds_recs, uint32_t* scan) {
+    walk_scan(st, h, keys, pos, total, node_base, lds_recs, scan, WalkFixed{});
+}
+__global__ __launch_bounds__(64) void k_walk_scan_live(VictState st, VictHdr h, const uint64_t* __restrict__ keys,
+                                                       int pos, int total, int node_base, int lds_recs,
+                                                       uint32_t* scan, WalkLive lv) {
+    walk_scan(st, h, keys, pos, total, node_base, lds_recs, scan, lv);
+}
 
 // kbhip_walk_next, the walk: one block.  first = min(scan[0], total).  Entries [pos, first) are passed over
 // and counted: no eviction of this call precedes them, so the overlay is empty and the scan's stateless
 // answer is the walk's.  From `first` the loop k_walk_victims_from runs, over at most `cap` entries of the
 // kept order: that entry too is decided by walk_step, and no entry after it by a flag.  s_res: the position
 // of the last entry passed over or acted on (an entry refused with kWalkCapacity is met again by the next call).
-__global__ __launch_bounds__(kWalkBlock) void k_walk_cursor(VictState st, VictHdr h0, const uint64_t* keys, int pos,
-                                                            int total, int cap, uint32_t* scan, int task,
-                                                            int node_base, VictRec* spill, int spill_stride,
-                                                            int ov_cap_j, int ov_cap_q, int64_t cap_ops,
-                                                            int64_t* out_info, int32_t* out_pod, int32_t* out_node) {
+// The live cursor's loop: the predicate is tested in front of walk_entry, on the tables the scan read — an
+// entry that fails is passed over, counted and gives no op (a spill-rule candidate among them) — and the
+// loop ends behind the first node acted on: that node's evictions change the count tables only through
+// kbhip_apply_ops, which the carried overlay cannot stand in for, so the entries behind it are the next
+// call's.  The stop reason then follows the position behind that node.  (Every branch is uniform over the
+// block and in front of walk_entry's barriers; thread 0 alone writes s.c and *res.)
+__device__ __forceinline__ void walk_loop_live(const VictState& st, WalkLds& s, const WalkArgs& a, const uint64_t* keys,
+                                               int i, int lim, uint64_t total, int* res, int64_t* out_info,
+                                               const WalkLive& lv) {
+    for (; i < lim; ++i) {
+        const uint64_t key = keys[i];
+        if (!walk_live_pred(lv, key)) {
+            if (threadIdx.x == 0) {
+                s.c.visited += 1;
+                *res = i;
+            }
+            continue;
+        }
+        walk_entry(st, s, a, key, i, res);
+        if (s.c.stop != 0 || s.c.acted != 0) break;
+    }
+    if (threadIdx.x != 0) return;
+    out_info[0] = s.c.stop != 0 ? s.c.stop : (uint64_t)(*res + 1) < total ? kWalkHeadEnd : kWalkExhausted;
+    out_info[1] = (int64_t)total;
+    out_info[2] = s.c.visited;
+    out_info[3] = s.c.acted;
+    out_info[6] = s.c.n_ops;
+}
+
+template <class L>
+__device__ __forceinline__ void walk_cursor(const VictState& st, const VictHdr& h0, const uint64_t* keys, int pos,
+                                            int total, int cap, uint32_t* scan, int task, int node_base,
+                                            VictRec* spill, int spill_stride, int ov_cap_j, int ov_cap_q,
+                                            int64_t cap_ops, int64_t* out_info, int32_t* out_pod, int32_t* out_node,
+                                            const L& lv) {
     __shared__ WalkLds s;
     __shared__ int s_res;
     const int tid = threadIdx.x;
@@ -368,8 +436,12 @@ __global__ __launch_bounds__(kWalkBlock) void k_walk_cursor(VictState st, VictHd
         s.c = WalkCtl{0, cap_ops, 0, first - pos, 0, -1, 0, task};
     }
     __syncthreads();
-    walk_loop<false>(st, s, WalkArgs{node_base, spill, spill_stride, out_pod, out_node}, keys, first, lim, cap, 0,
-                     (uint64_t)total, &s_res, out_info);
+    if constexpr (L::kLive)
+        walk_loop_live(st, s, WalkArgs{node_base, spill, spill_stride, out_pod, out_node}, keys, first, lim,
+                       (uint64_t)total, &s_res, out_info, lv);
+    else
+        walk_loop<false>(st, s, WalkArgs{node_base, spill, spill_stride, out_pod, out_node}, keys, first, lim, cap, 0,
+                         (uint64_t)total, &s_res, out_info);
     if (tid == 0) {
         out_info[4] = s_res + 1;
         out_info[5] = first < total ? first : -1;
@@ -379,6 +451,23 @@ __global__ __launch_bounds__(kWalkBlock) void k_walk_cursor(VictState st, VictHd
         scan[0] = ~0u;  // the two words as the next call's scan expects them (every thread read scan[0] before
         scan[1] = 0;    // the first barrier)
     }
+}
+__global__ __launch_bounds__(kWalkBlock) void k_walk_cursor(VictState st, VictHdr h0, const uint64_t* keys, int pos,
+                                                            int total, int cap, uint32_t* scan, int task,
+                                                            int node_base, VictRec* spill, int spill_stride,
+                                                            int ov_cap_j, int ov_cap_q, int64_t cap_ops,
+                                                            int64_t* out_info, int32_t* out_pod, int32_t* out_node) {
+    walk_cursor(st, h0, keys, pos, total, cap, scan, task, node_base, spill, spill_stride, ov_cap_j, ov_cap_q, cap_ops,
+                out_info, out_pod, out_node, WalkFixed{});
+}
+__global__ __launch_bounds__(kWalkBlock) void k_walk_cursor_live(VictState st, VictHdr h0, const uint64_t* keys,
+                                                                 int pos, int total, int cap, uint32_t* scan, int task,
+                                                                 int node_base, VictRec* spill, int spill_stride,
+                                                                 int ov_cap_j, int ov_cap_q, int64_t cap_ops,
+                                                                 int64_t* out_info, int32_t* out_pod,
+                                                                 int32_t* out_node, WalkLive lv) {
+    walk_cursor(st, h0, keys, pos, total, cap, scan, task, node_base, spill, spill_stride, ov_cap_j, ov_cap_q, cap_ops,
+                out_info, out_pod, out_node, lv);
 }
 
 // The scan's two words as k_walk_scan expects them: ~0 and 0 (kbhip_walk_begin; k_walk_cursor restores them).
@@ -390,15 +479,24 @@ hipError_t launch_walk_scan_init(uint32_t* scan, hipStream_t stm) {
 hipError_t launch_walk_cursor(const VictState& st, const VictHdr& h, const uint64_t* keys, int64_t pos, int64_t total,
                               int cap, int task, int node_base, int lds_recs, VictRec* spill, int spill_stride,
                               int ov_cap_j, int ov_cap_q, int64_t cap_ops, uint32_t* scan, int64_t* out_info,
-                              int32_t* out_pod, int32_t* out_node, hipStream_t stm) {
+                              int32_t* out_pod, int32_t* out_node, hipStream_t stm, const WalkLive* live) {
+    static_assert(sizeof(WalkLive) + sizeof(VictState) + sizeof(VictHdr) + 128 <= 4096, "the kernels' arguments");
     if (cap < 1 || cap > kTopK || cap_ops < 1 || lds_recs < 1 || lds_recs > kVictLds || pos < 0 || pos > total ||
         total > INT32_MAX || !keys || !scan)
         return hipErrorInvalidValue;
     // (an empty remainder still takes both launches: the call's launch count does not depend on its position)
     const int64_t left = total - pos;
-    hipLaunchKernelGGL(k_walk_scan, dim3(left < 1 ? 1u : left < kWalkScanBlocks ? (unsigned)left : (unsigned)kWalkScanBlocks),
-                       dim3(64),
-                       (size_t)lds_recs * sizeof(VictRec), stm, st, h, keys, (int)pos, (int)total, node_base, lds_recs,
+    const dim3 grid(left < 1 ? 1u : left < kWalkScanBlocks ? (unsigned)left : (unsigned)kWalkScanBlocks);
+    const size_t lds = (size_t)lds_recs * sizeof(VictRec);
+    if (live) {
+        hipLaunchKernelGGL(k_walk_scan_live, grid, dim3(64), lds, stm, st, h, keys, (int)pos, (int)total, node_base,
+                           lds_recs, scan, *live);
+        hipLaunchKernelGGL(k_walk_cursor_live, dim3(1), dim3(kWalkBlock), 0, stm, st, h, keys, (int)pos, (int)total,
+                           cap, scan, task, node_base, spill, spill_stride, ov_cap_j, ov_cap_q, cap_ops, out_info,
+                           out_pod, out_node, *live);
+        return hipGetLastError();
+    }
+    hipLaunchKernelGGL(k_walk_scan, grid, dim3(64), lds, stm, st, h, keys, (int)pos, (int)total, node_base, lds_recs,
                        scan);
     hipLaunchKernelGGL(k_walk_cursor, dim3(1), dim3(kWalkBlock), 0, stm, st, h, keys, (int)pos, (int)total, cap,
                        scan, task, node_base, spill, spill_stride, ov_cap_j, ov_cap_q, cap_ops,

@@ -1,6 +1,7 @@
 // kbhip session, part 19: a task's eviction walk over an order ranked once and kept on the device
 // (kbhip_walk_begin: kbhip_rank_victim_nodes' full sort and compaction, the keys left in a buffer the
-// cursor owns; kbhip_walk_next: every remaining entry decided side by side in one launch, the serial walk
+// cursor owns; kbhip_walk_begin_live: for reclaim's order and a class whose predicates read pod-affinity
+// targets, the order without that predicate, which kbhip_walk_next then tests per call; kbhip_walk_next: every remaining entry decided side by side in one launch, the serial walk
 // from the first one that can act; kbhip_walk_order: the kept order read back; kbhip_walk_end)
 #include "framework.h"
 
@@ -25,9 +26,15 @@ bool reads_affinity_targets(const TaskClass& c) { return c.ea_n > 0 || c.pa_spac
 // The ranking of rank_victim_nodes_abi's full path — rank_launch, then launch_vict_compact — with the
 // compaction's keys written straight into b_wc_keys (the candidate counts go to the shared scratch and are
 // not kept); the count and the sort's two counters come back in one wait.
-int64_t walk_begin_abi(Session& S, int pod, bool by_score, int mode, int64_t* out_info) {
-    const HPod& p = query_task(S, pod, "kbhip_walk_begin: the task ", true, "task id ");
-    query_begin(S, "kbhip_walk_begin");
+// live_call (kbhip_walk_begin_live, by_score false): a class that reads affinity targets gets a live cursor —
+// launch_live_keys' marks in place of the ranking (node order is the walk order: one launch, no sort), the
+// same compaction, and wc_live tells kbhip_walk_next to test the predicate left out; any other class takes
+// the path above unchanged.
+int64_t walk_begin_abi(Session& S, int pod, bool by_score, int mode, bool live_call, int64_t* out_info) {
+    const string api = live_call ? "kbhip_walk_begin_live" : "kbhip_walk_begin";
+    const HPod& p = query_task(S, pod, api + ": the task ", true, "task id ");
+    query_begin(S, api.c_str());
+    const bool reads = reads_affinity_targets(S.classes[p.cls]), live = live_call && reads;
     const int N = S.nc.n;
     const bool rebuilt = vict_ensure(S);
     vector<int32_t> own_node;
@@ -35,13 +42,21 @@ int64_t walk_begin_abi(Session& S, int pod, bool by_score, int mode, int64_t* ou
     const VictArgs v = vict_args(S, p, mode, own_node, own_sum);
     S.h_vict_out.fit(((size_t)N + 2) * sizeof(int32_t));
     int64_t launches = flush_tables(S);  // evictions / unevicts so far change pod-affinity predicates
-    launches += rank_launch(S, p.cls, by_score);
+    if (live) {
+        rank_buffers(S);
+        HIPCHK(launch_live_keys(S.conf, S.nc, S.tab, S.classes[p.cls], (uint64_t*)S.b_rank_keys.p,
+                                (uint32_t*)S.b_rank_cnt.p, S.stream));
+        launches += 1;
+    } else {
+        launches += rank_launch(S, p.cls, by_score);
+    }
+    const uint64_t* const ranked = (const uint64_t*)(live ? S.b_rank_keys.p : S.b_rank_sorted.p);
     vict_compact_buffers(S);
     const size_t key_bytes = (size_t)std::max(N, 1) * sizeof(uint64_t);
     S.wc_open = false;  // from here on the kept keys are overwritten: a failure leaves no cursor
     S.b_wc_keys.grow(S.stream, key_bytes, key_bytes);
     S.b_wc_scan.grow(S.stream, 2 * sizeof(uint32_t), 2 * sizeof(uint32_t));
-    HIPCHK(launch_vict_compact((const uint64_t*)S.b_rank_sorted.p, (const uint32_t*)S.b_rank_cnt.p, N, v,
+    HIPCHK(launch_vict_compact(ranked, (const uint32_t*)S.b_rank_cnt.p, N, v,
                                (uint32_t*)S.b_vict_blk.p, (uint64_t*)S.b_wc_keys.p, (int32_t*)S.b_vict_cands.p,
                                S.stream));
     HIPCHK(launch_walk_scan_init((uint32_t*)S.b_wc_scan.p, S.stream));
@@ -53,6 +68,7 @@ int64_t walk_begin_abi(Session& S, int pod, bool by_score, int mode, int64_t* ou
     HIPCHK(hipMemcpyAsync(h_rank, S.b_rank_cnt.p, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, S.stream));
     HIPCHK(hipStreamSynchronize(S.stream));
     if (h_rank[0] >> 32) throw Error(KBHIP_EDEVICE, "walk_begin: node score outside the class score range");
+    S.wc_live = live;
     S.wc_total = (int64_t)(uint32_t)h_out[0];
     S.wc_task = pod;
     S.wc_by_score = by_score;
@@ -62,7 +78,7 @@ int64_t walk_begin_abi(Session& S, int pod, bool by_score, int mode, int64_t* ou
         out_info[0] = launches;
         out_info[1] = rebuilt ? 1 : 0;
         out_info[2] = (int64_t)(S.b_wc_keys.req + S.b_wc_scan.req);
-        out_info[3] = reads_affinity_targets(S.classes[p.cls]) ? 1 : 0;
+        out_info[3] = live ? 2 : reads ? 1 : 0;
     }
     S.stats.sweeps++;
     return S.wc_total;
@@ -84,10 +100,12 @@ int64_t walk_next_abi(Session& S, int64_t pos, int cap, uint8_t* out_op, int32_t
         bool done = false;
         ~ScanGuard() { if (!done) S.wc_open = false; }
     } scan_guard{S};
+    // a live cursor: the class's pod-affinity predicate on the count tables state_prepare just made current
+    const WalkLive live{S.conf, S.nc, S.tab, S.classes[p.cls]};
     HIPCHK(launch_walk_cursor(vs_device_view(S), hp.h, (const uint64_t*)S.b_wc_keys.p, pos, S.wc_total, cap,
                               S.wc_task, S.nc.base, vs_lds_recs(S), vs_spill_rows(S), vs_spill_stride(S),
                               walk_ov_jobs(S), walk_ov_queues(S), o.dcap, (uint32_t*)S.b_wc_scan.p, o.info(),
-                              o.pods(), o.nodes(), S.stream));
+                              o.pods(), o.nodes(), S.stream, S.wc_live ? &live : nullptr));
     int64_t n;
     const int64_t* info = walk_finish(S, o, hp, out_op, out_pod, out_node, out_info, &n);
     scan_guard.done = true;
@@ -126,7 +144,14 @@ int64_t kbhip_walk_begin(kb_session* s, int32_t task_id, int32_t by_score, int32
     ABI_GUARD_S(s, {
         check_by_score("kbhip_walk_begin", by_score);
         check_victims("kbhip_walk_begin", victims);
-        return kbhip::walk_begin_abi(kbhip::device_session(s), task_id, by_score != 0, victims, out_info);
+        return kbhip::walk_begin_abi(kbhip::device_session(s), task_id, by_score != 0, victims, false, out_info);
+    })
+}
+
+int64_t kbhip_walk_begin_live(kb_session* s, int32_t task_id, int32_t victims, int64_t* out_info) {
+    ABI_GUARD_S(s, {
+        check_victims("kbhip_walk_begin_live", victims);
+        return kbhip::walk_begin_abi(kbhip::device_session(s), task_id, false, victims, true, out_info);
     })
 }
 

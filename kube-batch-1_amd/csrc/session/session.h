@@ -644,7 +644,8 @@ struct Session {
     // but the next kbhip_walk_begin; b_wc_scan: k_walk_scan's two words.  wc_open is cleared wherever the
     // candidate table and the victim state go stale (vict_stale): the order was ranked on statuses that call
     // changes.  A successful kbhip_apply_ops keeps it — those are the walk's own evictions.
-    bool wc_open = false, wc_by_score = false;
+    // wc_live: a cursor of kbhip_walk_begin_live whose kept order left the class's pod-affinity predicate out
+    bool wc_open = false, wc_by_score = false, wc_live = false;
     int32_t wc_task = -1, wc_mode = 0;
     int64_t wc_total = 0;
     DevBuf b_wc_keys, b_wc_scan;
@@ -1419,7 +1420,7 @@ int64_t walk_victims_from_abi(Session& S, int pod, bool by_score, int mode, int 
                               uint8_t* out_op, int32_t* out_pod, int32_t* out_node, int64_t cap_ops,
                               int64_t* out_info);
 // kbhip_walk_begin / kbhip_walk_next / kbhip_walk_order / kbhip_walk_end (19_walk_cursor.cpp)
-int64_t walk_begin_abi(Session& S, int pod, bool by_score, int mode, int64_t* out_info);
+int64_t walk_begin_abi(Session& S, int pod, bool by_score, int mode, bool live_call, int64_t* out_info);
 int64_t walk_next_abi(Session& S, int64_t pos, int cap, uint8_t* out_op, int32_t* out_pod, int32_t* out_node,
                       int64_t cap_ops, int64_t* out_info);
 int64_t walk_order_abi(Session& S, int64_t first, int32_t* out_node, int32_t* out_score, int64_t cap);

@@ -74,7 +74,8 @@ EXPORTS = ("kbhip_device_count", "kbhip_session_open", "kbhip_session_open_file"
            "kbhip_apply_ops", "kbhip_rank_victim_nodes", "kbhip_rank_heads", "kbhip_explain_tasks",
            "kbhip_debug_explain", "kbhip_head_victims", "kbhip_debug_victims", "kbhip_walk_victims",
            "kbhip_debug_walk_victims", "kbhip_heads_victims", "kbhip_walk_victims_from",
-           "kbhip_walk_begin", "kbhip_walk_next", "kbhip_walk_order", "kbhip_walk_end")
+           "kbhip_walk_begin", "kbhip_walk_next", "kbhip_walk_order", "kbhip_walk_end",
+           "kbhip_walk_begin_live")
 
 RED_MAX_U64, RED_MIN_I64, RED_MAX_I64, RED_SUM_I64 = 0, 1, 2, 3
 ALLREDUCE_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint64), ctypes.c_int32,
@@ -196,6 +197,8 @@ def lib() -> ctypes.CDLL:
         L.kbhip_walk_victims_from.restype = i64
         L.kbhip_walk_begin.argtypes = [vp, i32, i32, i32, vp]
         L.kbhip_walk_begin.restype = i64
+        L.kbhip_walk_begin_live.argtypes = [vp, i32, i32, vp]
+        L.kbhip_walk_begin_live.restype = i64
         L.kbhip_walk_next.argtypes = [vp, i64, i32, vp, vp, vp, i64, vp]
         L.kbhip_walk_next.restype = i64
         L.kbhip_walk_order.argtypes = [vp, i64, vp, vp, i64]
@@ -462,6 +465,18 @@ class Session:
         info: {"launches", "rebuilt", "bytes", "affinity_targets"}."""
         info = np.zeros(4, np.int64)
         n = int(lib().kbhip_walk_begin(self._h, int(task_id), int(by_score), int(victims), _p(info)))
+        _check(n if n < 0 else 0)
+        return n, dict(zip(("launches", "rebuilt", "bytes", "affinity_targets"), map(int, info)))
+
+    def walk_begin_live(self, task_id: int, victims: int = VICTIMS_OTHER_QUEUES):
+        """kbhip_walk_begin_live: the cursor for reclaim's order (by_score 0),
+        exact for every task class: (total, info) as walk_begin.  For a class
+        whose predicates read pod-affinity targets the cursor is live
+        (info["affinity_targets"] == 2): the kept order leaves that predicate
+        out, walk_next tests it per call and returns behind the first node it
+        acts on.  Any other class: walk_begin(task_id, False, victims)."""
+        info = np.zeros(4, np.int64)
+        n = int(lib().kbhip_walk_begin_live(self._h, int(task_id), int(victims), _p(info)))
         _check(n if n < 0 else 0)
         return n, dict(zip(("launches", "rebuilt", "bytes", "affinity_targets"), map(int, info)))
 
